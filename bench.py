@@ -1,15 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- G1 MSM/sec (BN254) on MI355X, the metric of BASELINE.json.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20] [--dump-outputs DIR] [--full]
 
 One "step" = one complete MultiExp (device-resident bases and scalars -> Jacobian result on the host) of
 n = 2^logn points.  N = 1: the whole MSM on one GPU (BASELINE config C2 at the default logn = 20).  N > 1 (one rank per GPU under
-torch.distributed.run; started as a plain `python bench.py --gpus N` the script re-executes itself under that launcher):
+torch.distributed.run; started as a plain `python bench.py --gpus N` the script starts that launcher as a child process):
 the SAME MSM is sharded over the ranks (points or windows, sharding.py), the per-window totals are exchanged with one
 RCCL all-gather and folded (strong scaling of one MSM, as BASELINE.json's north_star describes).
 
-Rank 0 prints one JSON line.  Besides the contract fields it carries
+A plain run sets up, runs W untimed and K timed steps, and rank 0 prints one JSON line with the contract fields only
+(metric, value = K / seconds of the timed steps, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling,
+vs_baseline, dtype, data, config).  The inputs are seeded by logn alone, so they are the same in every run.
+
+--dump-outputs DIR  after the timed steps, the result of the last one as DIR/msm_result_affine.npy: the point the timed
+                    entry returns, in affine form (x, y limbs of the Montgomery form; all zero = infinity), float64 with
+                    each uint64 limb split into its two 32-bit words, low word first, so every value is exact.  Affine,
+                    because the Jacobian coordinates the entry returns depend on the order in which the device summed
+                    (they differ between two runs of the same build); the affine point does not.
+
+--full adds everything beyond the headline: the full record goes to a side file (--full-out) and the printed line is
+tools/bench_line.py's slim line of it.  Besides the contract fields it carries
   value_cold / value_warm_bases   SURVEY.md §8(d): the same MSM through the drop-in C entries with host buffers
                 (cold: bases + scalars cross PCIe every call; warm-bases: registered bases, scalars cross PCIe)
   roofline      dominant kernel (k_accumulate_seg): algorithmic bytes per launch (96 B/point x n) /
@@ -77,6 +88,27 @@ def uniform_scalars(rng, g, n):
         sc[todo[lt]] = cand[lt]
         todo = todo[~lt]
     return sc
+
+
+def headline_inputs(g, logn):
+    """(points, scalars) of the timed MultiExp: synthetic, deterministic, on-curve: P_i = [k0 + i*k1] G,
+    scalars uniform.  Seeded by logn alone, so every run with the same arguments times the same MSM."""
+    rng = np.random.default_rng([0x6D736D, logn])
+    k0, k1 = int(rng.integers(1, 2**62)), int(rng.integers(1, 2**62))
+    pts = g.generate_points(1 << logn, k0, k1)
+    return pts, uniform_scalars(rng, g, 1 << logn)
+
+
+def u32_words(limbs):
+    """uint64 limbs -> float64 array of their 32-bit words (low word first): exact, unlike a float of a whole limb."""
+    limbs = np.asarray(limbs, dtype=np.uint64).reshape(-1)
+    return np.stack([limbs & np.uint64(0xFFFFFFFF), limbs >> np.uint64(32)], axis=-1).reshape(-1).astype(np.float64)
+
+
+def dump_outputs(dirname, g, jac):
+    """--dump-outputs: the last timed step's result (see the module docstring for the layout)."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "msm_result_affine.npy"), u32_words(g.jac_to_affine(jac)))
 
 
 STAGE_NOTE = ("accumulate: HIP events around k_accumulate_seg inside the timed region (two events per call); the other stages: "
@@ -871,7 +903,15 @@ def main():
     ap.add_argument("--full-out", default=None, help="where the full record goes (default bench_full_n<N>.json beside this file, and gpurun_out/)")
     ap.add_argument("--curve", default="bn254", help="exploration only: bn254 | bls12_381 | bw6_761")
     ap.add_argument("--group", default="g1", help="exploration only: g1 | g2")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the result of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (the --no-* switches, --batch and --full-out apply here)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.batch > 0 and not args.full:
+        ap.error("--batch is a measurement beyond the headline: add --full")
 
     # The contract is ONE JSON line on stdout. Native libraries write there too (RCCL prints a version banner to the C
     # stdout when the process exits, libdrm complains about amdgpu.ids): keep a private handle on the real stdout for the
@@ -886,8 +926,8 @@ def main():
 
     share = args.oversubscribe or os.environ.get("GMSM_BENCH_SHARE_DEVICE") == "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher (one rank per GPU, RCCL over xGMI); rank 0 of the
-        # relaunched job prints the JSON line on this process's stdout
+        # plain `python bench.py --gpus N`: start the launcher as a child process (one rank per GPU, RCCL over xGMI);
+        # rank 0 of that job prints the JSON line on this process's stdout
         have = torch.cuda.device_count()
         if have < args.gpus and not (share and have >= 1):
             raise SystemExit(f"bench.py --gpus {args.gpus}: needs {args.gpus} devices, this machine exposes {have} "
@@ -896,9 +936,11 @@ def main():
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.dup2(json_out.fileno(), 1)  # give the real stdout back to the ranks
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        import subprocess
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:],
+                             stdout=json_out.fileno())  # the real stdout for the ranks
+        sys.exit(rc if rc >= 0 else 128 - rc)  # a launcher killed by a signal exits as a shell reports it
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -929,11 +971,7 @@ def main():
     g = (gm.G1Jac if args.group == "g1" else gm.G2Jac)(args.curve)
     n = 1 << args.logn
 
-    # synthetic, deterministic, on-curve inputs: P_i = [k0 + i*k1] G; scalars uniform
-    rng = np.random.default_rng([0x6D736D, args.logn])
-    k0, k1 = int(rng.integers(1, 2**62)), int(rng.integers(1, 2**62))
-    pts = g.generate_points(n, k0, k1)
-    sc = uniform_scalars(rng, g, n)
+    pts, sc = headline_inputs(g, args.logn)
 
     d_pts = torch.from_numpy(pts.view(np.int64)).cuda()
     d_sc = torch.from_numpy(sc.view(np.int64)).cuda()
@@ -976,29 +1014,33 @@ def main():
 
     for _ in range(args.warmup):
         jac = step()
-    prof = StageProfile(lib, level=2)
-    prof.start()
+    prof = StageProfile(lib, level=2) if args.full else None  # --full: the roofline's kernel duration, live in the timed region
+    if prof:
+        prof.start()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         jac = step()
     barrier()
     dt = time.perf_counter() - t0
-    acc_only, acc_launches = prof.stop()
-    prof = StageProfile(lib)  # the stage breakdown: the same steps once more, outside the timed region
-    prof.start()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    stages, _ = prof.stop()
-    stages["accumulate"] = acc_only["accumulate"]  # the roofline's kernel duration is the timed region's
     if world > 1:
         dt = dist_max(torch, dist, dt)
+    if prof:
+        acc_only, acc_launches = prof.stop()
+        prof = StageProfile(lib)  # the stage breakdown: the same steps once more, outside the timed region
+        prof.start()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        stages, _ = prof.stop()
+        stages["accumulate"] = acc_only["accumulate"]  # the roofline's kernel duration is the timed region's
+    if args.dump_outputs and rank == 0:  # jac: the last timed step's result (the breakdown above does not replace it)
+        dump_outputs(args.dump_outputs, g, jac)
 
     # Two MultiExp calls in flight over resident bases (gmsm_multiexp_bases_submit/_collect): reported beside the
     # headline number, never instead of it. Every one of the K calls is submitted and collected inside the timed region.
     pipelined = None
-    if not sharded and not args.no_pipeline:
+    if args.full and not sharded and not args.no_pipeline:
         rb2 = resident or g.register_bases(d_points=d_pts.data_ptr(), n=n)
 
         def run_pipelined(k):
@@ -1064,7 +1106,7 @@ def main():
     # Replica mode (--batch K): K scalar vectors over the same registered bases, vector j on rank j % world, each rank
     # runs its share through gmsm_multiexp_bases_batch, ONE all-gather of the K Jacobian results.
     replica = None
-    if args.batch > 0:
+    if args.full and args.batch > 0:
         K = args.batch
         rbk = g.register_bases(d_points=d_pts.data_ptr(), n=n)
         d_vecs = d_sc.unsqueeze(0).repeat(len(sharding.owned_vectors(K, rank, world)) or 1, 1, 1).contiguous()
@@ -1092,7 +1134,7 @@ def main():
     # PCIe-inclusive rates of the drop-in entries (SURVEY.md §8(d) "cold" / "warm-bases"): host buffers in, result out.
     # First-class fields beside `value`, never instead of it.
     host_entry = None
-    if not sharded and rank == 0 and not args.no_host_entry:
+    if args.full and not sharded and rank == 0 and not args.no_host_entry:
         cfg = gm.MultiExpConfig()
         cold = median_ms(lambda: g.MultiExp(pts, sc, cfg))
         rb3 = resident or g.register_bases(d_points=d_pts.data_ptr(), n=n)
@@ -1108,14 +1150,14 @@ def main():
     # set): the resident-SRS path of kzg.Commit. Reported beside `value`, never instead of it - `value` is the entry that
     # takes the bases anew on every call, like the reference's MultiExp.
     tables = None
-    if not sharded and rank == 0 and not args.no_host_entry:
+    if args.full and not sharded and rank == 0 and not args.no_host_entry:
         tables = tables_record(gm, g, d_pts, d_sc, sc, n, stream, jac, args.steps)
 
     # The same MultiExp through the drop-in C entry with the library spreading it over the devices (one process): all
     # `world` devices driven by rank 0 while the other ranks wait on the host; on one GPU two logical ranks on device 0
     # (a functional check of the path, not a speed-up: both ranks share one device and one PCIe link).
     c_abi = None
-    if not args.no_host_entry:
+    if args.full and not args.no_host_entry:
         def through_the_c_abi():
             return c_abi_sharded(gm, g, pts, sc, rank_devices if world > 1 else [dev_index, dev_index], g.jac_to_affine(jac))
         if world > 1:
@@ -1127,11 +1169,11 @@ def main():
     # N > 1: the 2^24 half of BASELINE.json's metric, sharded the same way (every rank takes part; rank 0 reports)
     also_sharded, sharded_rows = None, []
     headline_parts = None
-    if sharded:
+    if args.full and sharded:
         # the headline's stage times (max over ranks) and its exchange, cut at the joints (outside the timed loop)
         stages = max_over_ranks(dist, world, stages)
         headline_parts = max_over_ranks(dist, world, exchange_breakdown(torch, g, sharding, plan, enqueue, exchange))
-    if sharded and not args.no_also and (args.curve, args.group) == ("bn254", "g1"):
+    if args.full and sharded and not args.no_also and (args.curve, args.group) == ("bn254", "g1"):
         del d_pts_loc, d_sc_loc
         logns = sorted({int(x) for x in args.sharded_logns.split(",") if x} | {args.also_logn})
         for ln in logns:
@@ -1144,8 +1186,6 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = args.steps / dt
-        # this rank's share of the (point, window) pairs: all windows of its slice, or its windows of all points
-        my_pairs = (plan["hi"] - plan["lo"]) * len(range(plan["win_first"], nwin, plan["win_stride"])) if sharded else n * nwin * epp
         out = {
             "metric": "G1 MSM/sec (BN254)" if (args.curve, args.group) == ("bn254", "g1") else f"{args.group.upper()} MSM/sec ({args.curve})",
             "value": value, "unit": "MSM/s", "n_gpus": world, "steps": args.steps,
@@ -1156,6 +1196,14 @@ def main():
                        "points": n, "window_bits": c, "windows": nwin, "glv_half_scalars": epp == 2, "resident_bases": resident is not None,
                        "parallelism": "single GPU" if not sharded else
                                       f"{plan['mode']}-sharded x{world} + one {'RCCL' if backend == 'nccl' else backend} all-gather"},
+        }
+    if rank == 0 and not args.full:
+        from tools import bench_line
+        print(bench_line.encode(bench_line.contract_line(out)), file=json_out, flush=True)
+    if rank == 0 and args.full:
+        # this rank's share of the (point, window) pairs: all windows of its slice, or its windows of all points
+        my_pairs = (plan["hi"] - plan["lo"]) * len(range(plan["win_first"], nwin, plan["win_stride"])) if sharded else n * nwin * epp
+        out.update({
             "value_cold": host_entry["cold_msm_per_s"] if host_entry else None,
             "value_warm_bases": host_entry["warm_bases_msm_per_s"] if host_entry else None,
             "points_per_s": value * n,
@@ -1170,7 +1218,7 @@ def main():
             "roofline": roofline_record(g, n, my_pairs / (n * nwin * epp), stages, acc_launches,
                                         measured_traffic(args.curve, args.group, args.logn, world, nwin)),
             "int_roofline": int_roofline_record(g, my_pairs, stages["accumulate"]),
-        }
+        })
         tail = {}
         if sharded:
             # what the process group really was: the SCALE record shows that RCCL saw N ranks on N devices

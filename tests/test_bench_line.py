@@ -75,3 +75,13 @@ def test_validator_flags_what_the_driver_would_trip_over():
     fitted = bench_line.fit(dict(good, padding2="y" * 3000))  # sheds optional blocks, never the measurement blocks
     assert "roofline" in fitted and "cpu_baseline" in fitted and "int_roofline" in fitted
     assert bench_line.validate(bench_line.encode(full)) != []  # the round-5 line itself: too long
+
+
+def test_contract_line_carries_the_contract_keys_alone():
+    full = load(CANNED_N1[0])
+    d = bench_line.contract_line(full)
+    assert set(d) == set(bench_line.CONTRACT_KEYS) | {"arithmetic"}
+    assert bench_line.validate(bench_line.encode(d), n1_requirements=False) == []
+    assert d["value"] == pytest.approx(full["value"], rel=1e-3) and d["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-3)
+    assert {k: d[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps")} == \
+        {k: full[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps")}

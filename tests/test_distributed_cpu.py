@@ -239,6 +239,23 @@ def test_bench_launcher_asks_for_the_devices_it_needs():
     assert r.returncode != 0 and "must agree" in (r.stderr + r.stdout)
 
 
+def test_bench_refuses_arguments_it_cannot_honour():
+    """--steps sets the number of timed steps: none is an error, not a division by zero; --batch only runs under --full."""
+    import subprocess
+    for args, text in ((["--steps", "0"], "--steps"), (["--warmup", "-1"], "--warmup"), (["--batch", "2"], "--full")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and text in r.stderr, (args, r.stderr[-2000:])
+
+
+def test_bench_dumps_limbs_as_exact_words():
+    import bench
+    limbs = np.array([0, 1, 0xFFFFFFFF, 1 << 32, 0xFFFFFFFFFFFFFFFF, 0x0123456789ABCDEF], dtype=np.uint64)
+    words = bench.u32_words(limbs)
+    assert words.dtype == np.float64 and words.shape == (2 * len(limbs),)
+    back = words.astype(np.uint64).reshape(-1, 2)
+    assert ((back[:, 0] | (back[:, 1] << np.uint64(32))) == limbs).all()
+
+
 def test_bench_sharded_inputs_are_the_same_on_every_rank(gm):
     """bench.py's N > 1 rows generate their synthetic inputs per rank and per chunk (chunked_scalars): whatever the point
     slices, the ranks must see slices of ONE array - otherwise the closed-form check (every rank contributes the dot product

@@ -1,8 +1,9 @@
 """What can be checked of the Go side of the boundary without a Go toolchain (integration/go/<curve>/): the file-level
 build tags exclude each other, package names match the reference's packages, every C symbol a stub calls is declared in
 include/gmsm.h and exported by libgmsm.so, the three curve directories are the same file up to the documented
-substitutions, and the reference really defines the methods the recipe renames at the cited lines (when the reference
-tree is present - it is not on the GPU box)."""
+substitutions, and the reference really defines the methods the recipe renames at the cited lines (line numbers recorded
+from the reference in tests/golden/reference_facts.json by tests/golden/make_reference_facts.py)."""
+import json
 import os
 import re
 
@@ -10,6 +11,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GO = os.path.join(ROOT, "integration", "go")
+with open(os.path.join(ROOT, "tests", "golden", "reference_facts.json")) as _f:
+    REF_FACTS = json.load(_f)
 CURVES = {"bn254": ("bn254", "gmsm_bn254_", "ecc/bn254", (32, 357)),
           "bls12-381": ("bls12381", "gmsm_bls12_381_", "ecc/bls12-381", (32, 355)),
           "bw6-761": ("bw6761", "gmsm_bw6_761_", "ecc/bw6-761", (32, 306))}
@@ -51,16 +54,12 @@ def test_stub_files_are_consistent(gm, curve):
 @pytest.mark.parametrize("curve", sorted(CURVES))
 def test_recipe_matches_the_reference(curve):
     pkg, _, path, lines = CURVES[curve]
-    ref = os.path.join("/root/reference", path, "multiexp.go")
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present (GPU box)")
-    src = open(ref).read().splitlines()
-    assert src[lines[0] - 1].startswith("func (p *G1Jac) MultiExp(")
-    assert src[lines[1] - 1].startswith("func (p *G2Jac) MultiExp(")
-    assert any(re.match(rf"^package {pkg}$", ln) for ln in src[:12])
-    tmpl = open("/root/reference/internal/generator/ecc/template/multiexp.go.tmpl").read().splitlines()
-    assert tmpl[247 - 1].startswith("func (p *{{ $.TJacobian }}) MultiExp(")
-    assert "_p.MultiExp(points[:nbPoints/2]" in tmpl[350 - 1] and "p.MultiExp(points[nbPoints/2:]" in tmpl[353 - 1]
+    src = REF_FACTS["lines"][f"{path}/multiexp.go"]
+    assert (src.get("G1Jac.MultiExp"), src.get("G2Jac.MultiExp")) == lines
+    assert REF_FACTS["package"][f"{path}/multiexp.go"] == pkg
+    tmpl = REF_FACTS["lines"]["internal/generator/ecc/template/multiexp.go.tmpl"]
+    assert tmpl.get("TJacobian.MultiExp") == 247
+    assert tmpl.get("MultiExp of the first half") == 350 and tmpl.get("MultiExp of the second half") == 353
 
 
 # ---- N1 on the Go side: the resident proving key of package kzg (integration/go/<curve>/kzg/)
@@ -119,21 +118,17 @@ def test_kzg_resident_key_files(gm, curve):
 @pytest.mark.parametrize("curve", sorted(CURVES))
 def test_kzg_files_cite_the_reference(curve):
     path = CURVES[curve][2]
-    ref = os.path.join("/root/reference", path, "kzg")
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present (GPU box)")
-    kzg = open(os.path.join(ref, "kzg.go")).read().splitlines()
-    assert kzg[159 - 1].startswith("func Commit(p []fr.Element, pk ProvingKey, nbTasks ...int) (Digest, error)")
-    assert "res.MultiExp(pk.G1[:len(p)], p, config)" in "\n".join(kzg[159:176])
-    assert kzg[180 - 1].startswith("func Open(") and kzg[246 - 1].startswith("func BatchOpenSinglePoint(")
-    assert any("ErrInvalidPolynomialSize" in ln for ln in kzg[:40]) and any("ErrMinSRSSize" in ln for ln in kzg[:40])
-    marshal = open(os.path.join(ref, "marshal.go")).read().splitlines()
-    assert marshal[98 - 1].startswith("func (srs *SRS) ReadDump(") and "unsafe.ReadSlice" in "\n".join(marshal[98:113])
+    within = lambda at, first, last: at is not None and first <= at <= last
+    kzg = REF_FACTS["lines"][f"{path}/kzg/kzg.go"]
+    assert kzg.get("Commit") == 159 and within(kzg.get("Commit: MultiExp over pk.G1"), 160, 176)
+    assert kzg.get("Open") == 180 and kzg.get("BatchOpenSinglePoint") == 246
+    assert within(kzg.get("ErrInvalidPolynomialSize"), 1, 40) and within(kzg.get("ErrMinSRSSize"), 1, 40)
+    marshal = REF_FACTS["lines"][f"{path}/kzg/marshal.go"]
+    assert marshal.get("SRS.ReadDump") == 98 and within(marshal.get("ReadDump: unsafe.ReadSlice"), 99, 113)
     # ReadFromResident's twins and the stream they read
-    assert marshal[16 - 1].startswith("func (pk *ProvingKey) WriteTo(") and "enc.Encode(pk.G1)" in "\n".join(marshal[16:32])
-    assert marshal[140 - 1].startswith("func (pk *ProvingKey) ReadFrom(") and "dec.Decode(&pk.G1)" in "\n".join(marshal[140:147])
-    assert marshal[151 - 1].startswith("func (pk *ProvingKey) UnsafeReadFrom(") and "NoSubgroupChecks()" in "\n".join(marshal[151:158])
-    dec = open(os.path.join("/root/reference", path, "marshal.go")).read()
-    assert "unsafeComputeY(dec.subGroupCheck)" in dec and "func isCompressed(msb byte) bool" in dec
-    g1 = open(os.path.join("/root/reference", path, "g1.go")).read()
-    assert "func BatchJacobianToAffineG1(points []G1Jac) []G1Affine" in g1
+    assert marshal.get("ProvingKey.WriteTo") == 16 and within(marshal.get("WriteTo: encode pk.G1"), 17, 32)
+    assert marshal.get("ProvingKey.ReadFrom") == 140 and within(marshal.get("ReadFrom: decode pk.G1"), 141, 147)
+    assert marshal.get("ProvingKey.UnsafeReadFrom") == 151 and within(marshal.get("UnsafeReadFrom: NoSubgroupChecks"), 152, 158)
+    dec = REF_FACTS["lines"][f"{path}/marshal.go"]
+    assert "Decoder: unsafeComputeY with the subgroup check" in dec and "isCompressed" in dec
+    assert "BatchJacobianToAffineG1" in REF_FACTS["lines"][f"{path}/g1.go"]

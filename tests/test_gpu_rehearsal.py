@@ -36,7 +36,8 @@ def test_bench_sharded_branch_oversubscribed(world, extra, tmp_path):
     sys.path.insert(0, ROOT)
     from tools import bench_line
     full_path = str(tmp_path / "full.json")
-    slim, line = run_bench("--gpus", str(world), "--oversubscribe", "--steps", "3", "--warmup", "1", "--full-out", full_path, *extra)
+    slim, line = run_bench("--gpus", str(world), "--oversubscribe", "--full", "--steps", "3", "--warmup", "1", "--full-out", full_path,
+                           *extra)
     # the printed line: bounded, schema-clean, and carrying the verdict fields in compact form
     assert len(line.encode()) <= bench_line.MAX_LINE_BYTES and bench_line.validate(line) == []
     assert slim["n_gpus"] == world and slim["backend"] == "gloo" and slim["equal_to_single_gpu_result"] is True
@@ -75,3 +76,30 @@ def test_bench_refuses_more_ranks_than_devices_without_the_switch():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)], cwd=ROOT, capture_output=True,
                        text=True, timeout=300, env={k: v for k, v in os.environ.items() if k != "GMSM_BENCH_SHARE_DEVICE"})
     assert p.returncode != 0 and f"needs {n} devices" in p.stderr
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run_prints_the_contract_and_dumps_the_last_result(world, tmp_path, gm, oracle_mod):
+    """A plain run (no --full) prints the contract keys alone; --dump-outputs holds the last timed step's result, which is
+    the MultiExp of bench.headline_inputs - on one GPU and sharded over two ranks alike."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from tools import bench_line
+    logn, out_dir = 16, tmp_path / "out"
+    args = ["--steps", "3", "--warmup", "1", "--logn", str(logn), "--dump-outputs", str(out_dir)]
+    slim, line = run_bench(*(["--gpus", str(world), "--oversubscribe"] if world > 1 else []), *args)
+    assert set(slim) == set(bench_line.CONTRACT_KEYS) | {"arithmetic"}
+    assert bench_line.validate(line, n1_requirements=False) == []
+    assert slim["steps"] == 3 and slim["warmup"] == 1 and slim["n_gpus"] == world and slim["ms_per_step"] > 0
+    assert os.listdir(out_dir) == ["msm_result_affine.npy"]
+    dumped = np.load(out_dir / "msm_result_affine.npy")
+    assert dumped.dtype == np.float64
+
+    def limbs(words):  # the inverse of bench.u32_words
+        w = words.astype(np.uint64).reshape(-1, 2)
+        return w[:, 0] | (w[:, 1] << np.uint64(32))
+    g = gm.G1Jac("bn254")
+    pts, sc = bench.headline_inputs(g, logn)
+    exp = oracle_mod.Oracle("bn254", "g1").msm_affine(pts, sc, nthreads=4)
+    assert (limbs(dumped) == exp).all()

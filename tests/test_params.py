@@ -1,14 +1,13 @@
-"""Curve/field constants: re-derived from the moduli, and (where the reference tree exists) compared with the
-constants gnark-crypto's generator emitted."""
+"""Curve/field constants: re-derived from the moduli, and compared with the constants gnark-crypto's generator emitted
+(recorded in tests/golden/reference_facts.json)."""
 import importlib
+import json
 import os
 import re
 
 import pytest
 
 curves = importlib.import_module("gnark-crypto_amd.curves")
-REF = "/root/reference/ecc"
-REF_DIR = {"bn254": "bn254", "bls12_381": "bls12-381", "bw6_761": "bw6-761"}
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -63,21 +62,19 @@ def test_params32_header_consistent():
             assert (qinv * q + 1) % (1 << 32) == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", list(curves.CURVES))
 def test_constants_match_reference(name):
     c = curves.CURVES[name]
+    with open(os.path.join(ROOT, "tests", "golden", "reference_facts.json")) as f:
+        ref = json.load(f)["constants"][name]  # fp/element.go, fr/element.go (tests/golden/make_reference_facts.py)
     for fld, q, n in (("fp", c.p, c.fp_limbs), ("fr", c.r, c.fr_limbs)):
-        txt = open(os.path.join(REF, REF_DIR[name], fld, "element.go")).read()
-        limbs = [int(re.search(rf"\bq{i}\s*(?:uint64)?\s*=\s*(\d+)", txt).group(1)) for i in range(n)]
-        assert sum(l << (64 * i) for i, l in enumerate(limbs)) == q
-        qinv = int(re.search(r"const qInvNeg\s*(?:uint64)?\s*=\s*(\d+)", txt).group(1))
+        limbs = ref[fld]["q"]
+        assert len(limbs) == n and sum(l << (64 * i) for i, l in enumerate(limbs)) == q
+        qinv = ref[fld]["q_inv_neg"]
         assert (qinv * q + 1) % (1 << 64) == 0
         assert qinv == (-pow(q, -1, 1 << 64)) % (1 << 64)
-        assert int(re.search(r"Limbs\s*=\s*(\d+)", txt).group(1)) == n
-        assert int(re.search(r"Bits\s*=\s*(\d+)", txt).group(1)) == q.bit_length()
-        # rSquare: first limb is listed in the source
-        m = re.search(r"var rSquare = Element\{\s*((?:\d+,\s*)+)\}", txt)
-        rs = [int(x) for x in re.findall(r"\d+", m.group(1))]
+        assert ref[fld]["limbs"] == n
+        assert ref[fld]["bits"] == q.bit_length()
+        rs = ref[fld]["r_square"]
         R = 1 << (64 * n)
         assert sum(l << (64 * i) for i, l in enumerate(rs)) == R * R % q

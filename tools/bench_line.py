@@ -1,5 +1,6 @@
 """The ONE JSON line bench.py prints, assembled from the full record of a run.
 
+A plain bench.py run prints contract_line(record): the contract keys alone.  With --full:
 The driver parses the line it reads from stdout and keeps a bounded copy: round 5's N = 1 line had grown to 26 KB and came back
 `parsed: null`. bench.py therefore builds the full record as before, writes it to a side file (bench_full_n<N>.json, copied under
 profiles/ per round), and prints slim_line(full): the contract keys, `roofline`, `int_roofline`, `cpu_baseline`, the headline's
@@ -93,8 +94,8 @@ def compact_also_row(r):
     return row
 
 
-def slim_line(full, full_path=None):
-    """The dict bench.py prints: every key the driver's contract names, the three measurement blocks, compact rows."""
+def contract_line(full):
+    """The dict a plain bench.py run prints: every key the driver's contract names, nothing measured beyond the headline."""
     out = {k: full.get(k) for k in CONTRACT_KEYS}
     out["value"] = _r(out["value"])
     out["ms_per_step"] = _r(out["ms_per_step"])
@@ -102,6 +103,12 @@ def slim_line(full, full_path=None):
     cfg.pop("arithmetic", None)
     out["config"] = cfg
     out["arithmetic"] = "Montgomery field on lazy 28/29-bit limbs in u32 words (v_mad_u64_u32)"
+    return out
+
+
+def slim_line(full, full_path=None):
+    """The dict bench.py --full prints: the contract keys, the three measurement blocks, compact rows."""
+    out = contract_line(full)
     for k in ("value_cold", "value_warm_bases", "value_tables", "bit_exact", "backend", "rccl_ranks", "devices_seen", "device_count",
               "oversubscribed", "equal_to_single_gpu_result", "compute_ms", "exchange_ms"):
         if k in full:

@@ -3,7 +3,7 @@
 # (one parametrised script instead of a numbered script per session). Steps:
 #   suite        pytest -m gpu (GMSM_REQUIRE_SANITIZERS=1: the sanitizer tests fail instead of skipping)
 #   smoke        __graft_entry__.smoke()
-#   bench        python bench.py (default line)
+#   bench        python bench.py --full (the full record and its slim line)
 #   dist         tools/bench_distributions.py (BN254 G1 2^20 + 2^24, all distributions)
 #   dist_g2      ... BLS12-381 G2 2^22, uniform + smallvalues
 #   dist_prof    rocprofv3 kernel stats of the smallvalues rows (2^20, 2^24)
@@ -21,7 +21,7 @@ for step in "$@"; do
     suite)   ( GMSM_REQUIRE_SANITIZERS=1 timeout 2400 python -m pytest tests -m gpu -x -q -rs > $O/gputest.log 2>&1; echo "pytest rc=$?" >> $O/gputest.log ); tail -4 $O/gputest.log
              cp gpurun_out/sanitizer_*.log $O/ 2>/dev/null ;;
     smoke)   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log ;;
-    bench)   ( timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/bench.err ); tail -c 900 $O/bench.json; echo; tail -2 $O/bench.err ;;
+    bench)   ( timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/bench.err ); tail -c 900 $O/bench.json; echo; tail -2 $O/bench.err ;;
     dist)    timeout 900 python tools/bench_distributions.py > $O/dist.json 2> $O/dist.log; cat $O/dist.log | grep -v Warning ;;
     dist_g2) timeout 900 python tools/bench_distributions.py bls12_381 g2 22 3 --kinds=uniform,smallvalues --no-cold > $O/dist_g2.json 2> $O/dist_g2.log; grep -v Warning $O/dist_g2.log ;;
     dist_prof)
