@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "gmsm_get_stage_launches", "gmsm_points_from_raw", "gmsm_points_validate", "gmsm_bases_register_raw",
     "gmsm_points_from_compressed", "gmsm_points_compress", "gmsm_bases_register_compressed",
     "gmsm_bases_register_dump", "gmsm_fft_domain_new", "gmsm_fft_domain_release", "gmsm_fft_domain_info", "gmsm_fft",
-    "gmsm_fft_bit_reverse",
+    "gmsm_fft_bit_reverse", "gmsm_poly_eval", "gmsm_poly_div_x_minus_a", "gmsm_kzg_open", "gmsm_kzg_open_folded",
     "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
     "gmsm_device_count", "gmsm_set_device", "gmsm_last_error",
@@ -164,6 +164,15 @@ def load():
     L.gmsm_fft.argtypes = [ctypes.c_uint64, u64p, vp, sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
     L.gmsm_fft_bit_reverse.restype = ctypes.c_int
     L.gmsm_fft_bit_reverse.argtypes = [ctypes.c_int, u64p, vp, sz, vp]
+    szp = ctypes.POINTER(sz)
+    L.gmsm_poly_eval.restype = ctypes.c_int
+    L.gmsm_poly_eval.argtypes = [ctypes.c_int, u64p, vp, szp, sz, u64p, vp, u64p]
+    L.gmsm_poly_div_x_minus_a.restype = ctypes.c_int
+    L.gmsm_poly_div_x_minus_a.argtypes = [ctypes.c_int, u64p, vp, sz, u64p, vp, u64p, vp, u64p]
+    L.gmsm_kzg_open.restype = ctypes.c_int
+    L.gmsm_kzg_open.argtypes = [ctypes.c_uint64, u64p, vp, sz, u64p, vp, u64p, u64p]
+    L.gmsm_kzg_open_folded.restype = ctypes.c_int
+    L.gmsm_kzg_open_folded.argtypes = [ctypes.c_uint64, u64p, vp, szp, sz, u64p, u64p, vp, u64p]
     L.gmsm_get_stage_launches.restype = ctypes.c_int
     L.gmsm_get_stage_launches.argtypes = [vp, ctypes.c_int]
     ip = ctypes.POINTER(ctypes.c_int)

@@ -179,6 +179,7 @@ struct Workspace {
     size_t pinned_cap = 0;
     DeviceBuffer h2d_points, h2d_scalars;  // staging of the host-pointer entries
     DeviceBuffer raw_bytes, flagword;      // point ingest: wire-format bytes, first-offender word
+    DeviceBuffer poly;                     // KZG opening (gmsm_poly.h): folded polynomial, quotient, lane and tile carries
     bool busy = false;  // leased to a call (Context::acquire / release)
     bool ticket = false;  // ... by gmsm_multiexp_bases_submit: only gmsm_multiexp_collect ends that lease
     // state of a submitted, not yet collected call
@@ -198,7 +199,7 @@ struct Workspace {
     size_t trim(size_t keep) {
         DeviceBuffer *all[] = {&upoints, &skip, &seg_lvl, &seg_partials, &seg_flags, &seg_bucket, &parted, &heavy, &long_pieces, &small_sums, &small_done, &digits, &sorted,
                                &blockhist, &counts, &starts, &buckets, &partials, &totals, &red_pre, &carry, &h2d_points,
-                               &h2d_scalars, &raw_bytes, &flagword};
+                               &h2d_scalars, &raw_bytes, &flagword, &poly};
         size_t freed = 0;
         for (DeviceBuffer *b : all)
             if (b->cap > keep) freed += b->release();
@@ -688,6 +689,15 @@ struct GroupVTable {
     unsigned (*host_piece_ranges)(size_t n, bool with_points);  // point ranges a host-buffer piece of n points runs as
     int (*debug_glv_split)(const uint64_t *scalars, size_t n, uint32_t *out);  // test hook of gmsm_glv.h
     void (*plan_info)(size_t n, unsigned *c, unsigned *nwin, unsigned *entries_per_point, unsigned *fused);  // gmsm_default_plan
+    // KZG opening over the group's scalar field (gmsm_poly.h): polynomials are host (`polys`) or device (`d_polys`) fr.Element
+    // vectors, k of them concatenated (lens[i] elements each), never modified
+    int (*poly_eval)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
+                     hipStream_t stream, uint64_t *out_values);
+    int (*poly_div)(Context &ctx, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point, hipStream_t stream,
+                    uint64_t *out_h, void *d_out_h, uint64_t *out_value);
+    // H = MultiExp(resident[:maxlen - 1], (sum_i gamma^i f_i) / (X - point)); gamma == nullptr: k == 1, no fold
+    int (*kzg_open)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
+                    const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed, uint64_t *out_jac, const ResidentBases *resident);
 };
 
 }  // namespace gmsm

@@ -1326,6 +1326,98 @@ GMSM_EXPORT int gmsm_fft_bit_reverse(int group, uint64_t *a, void *d_a, size_t n
     return GMSM_OK;
 }
 
+// ------------------------------------------------------------------ KZG opening (gmsm_poly.h)
+static const char *const ERR_POLY_SIZE = "invalid polynomial size (larger than SRS or == 0)";  // ErrInvalidPolynomialSize, kzg.go
+
+// d must be 16-byte aligned device memory of `device` (a vector elsewhere would fault or read garbage)
+static int check_device_vector(const char *entry, const char *name, const void *d, int device) {
+    if (!d) return GMSM_OK;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, d) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device) {
+        (void)hipGetLastError();
+        return fail(GMSM_ERR_ARG, std::string(entry) + ": " + name + " is not device memory of the call's device");
+    }
+    if ((uintptr_t)d % 16) return fail(GMSM_ERR_ARG, std::string(entry) + ": " + name + " is not 16-byte aligned");
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_poly_eval(int group, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                               const uint64_t *point, void *hip_stream, uint64_t *out_values) {
+    VT_OR_FAIL(group);
+    if (k == 0) return GMSM_OK;
+    if (!lens || !point || !out_values) return fail(GMSM_ERR_ARG, "gmsm_poly_eval: lens, point and out_values must not be null");
+    if ((polys == nullptr) == (d_polys == nullptr))
+        return fail(GMSM_ERR_ARG, "gmsm_poly_eval: give exactly one of polys (host) / d_polys (device)");
+    if (polys && polys == out_values) return fail(GMSM_ERR_ARG, "gmsm_poly_eval: out_values aliases polys (inputs are never modified)");
+    for (size_t i = 0; i < k; ++i)
+        if (lens[i] == 0) return fail(GMSM_ERR_ARG, "gmsm_poly_eval: polynomial " + std::to_string(i) + " is empty (eval reads p[len(p)-1])");
+    Context *ctx;
+    int rc = get_context_of_pointer(d_polys, &ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector("gmsm_poly_eval", "d_polys", d_polys, ctx->device))) return rc;
+    return vt->poly_eval(*ctx, polys, d_polys, lens, k, point, (hipStream_t)hip_stream, out_values);
+}
+
+GMSM_EXPORT int gmsm_poly_div_x_minus_a(int group, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point,
+                                        void *hip_stream, uint64_t *out_h, void *d_out_h, uint64_t *out_value) {
+    VT_OR_FAIL(group);
+    const char *E = "gmsm_poly_div_x_minus_a";
+    if (n == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": n == 0 (f(a) of an empty polynomial is undefined)");
+    if (!point) return fail(GMSM_ERR_ARG, std::string(E) + ": point is null");
+    if ((poly == nullptr) == (d_poly == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of poly (host) / d_poly (device)");
+    if (n > 1 && (out_h == nullptr) == (d_out_h == nullptr))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_h (host) / d_out_h (device)");
+    if ((poly && (poly == out_h || poly == out_value)) || (d_poly && d_poly == d_out_h) || (out_h && out_h == out_value))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": an output aliases the input or another output (inputs are never modified)");
+    Context *ctx;
+    int rc = get_context_of_pointer(d_poly ? d_poly : d_out_h, &ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_poly", d_poly, ctx->device)) || (rc = check_device_vector(E, "d_out_h", n > 1 ? d_out_h : nullptr, ctx->device)))
+        return rc;
+    return vt->poly_div(*ctx, poly, d_poly, n, point, (hipStream_t)hip_stream, n > 1 ? out_h : nullptr, n > 1 ? d_out_h : nullptr, out_value);
+}
+
+// Open (kzg.go:180-205) and the part of BatchOpenSinglePoint after the challenge (:246-339) over registered bases
+static int kzg_open_impl(const char *E, uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                         const uint64_t *point, const uint64_t *gamma, void *hip_stream, uint64_t *out_claimed, uint64_t *out_h_jac) {
+    if (k == 0 || !lens) return fail(GMSM_ERR_ARG, std::string(E) + ": no polynomial");
+    size_t maxlen = 0;
+    for (size_t i = 0; i < k; ++i) {
+        if (lens[i] == 0) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);
+        maxlen = std::max(maxlen, lens[i]);
+    }
+    if (maxlen < 2) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);  // Commit of the empty quotient refuses it
+    if (!point || !out_h_jac || (k > 1 && !gamma)) return fail(GMSM_ERR_ARG, std::string(E) + ": point, gamma and out_h_jac must not be null");
+    if ((polys == nullptr) == (d_polys == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of polys (host) / d_polys (device)");
+    if (out_claimed && (out_claimed == out_h_jac || out_claimed == polys))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": out_claimed aliases another argument");
+    if (polys && polys == out_h_jac) return fail(GMSM_ERR_ARG, std::string(E) + ": out_h_jac aliases polys (inputs are never modified)");
+    BasesRef rb = lookup_bases(handle);
+    if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
+    if (maxlen > rb->n) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);
+    const GroupVTable *vt = vtable(rb->group);
+    Context *ctx;
+    int rc = get_context_for(rb->device, &ctx);  // the bases decide the device
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
+    return vt->kzg_open(*ctx, polys, d_polys, lens, k, point, k > 1 ? gamma : nullptr, (hipStream_t)hip_stream, out_claimed, out_h_jac,
+                        rb.get());
+}
+
+GMSM_EXPORT int gmsm_kzg_open(uint64_t handle, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point,
+                              void *hip_stream, uint64_t *out_claimed, uint64_t *out_h_jac) {
+    if (!out_claimed) return fail(GMSM_ERR_ARG, "gmsm_kzg_open: out_claimed is null");
+    return kzg_open_impl("gmsm_kzg_open", handle, poly, d_poly, &n, 1, point, nullptr, hip_stream, out_claimed, out_h_jac);
+}
+
+GMSM_EXPORT int gmsm_kzg_open_folded(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                                     const uint64_t *point, const uint64_t *gamma, void *hip_stream, uint64_t *out_h_jac) {
+    return kzg_open_impl("gmsm_kzg_open_folded", handle, polys, d_polys, lens, k, point, gamma, hip_stream, nullptr, out_h_jac);
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {

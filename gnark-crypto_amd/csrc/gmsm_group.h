@@ -19,6 +19,7 @@
 #include "gmsm_ingest.h"
 #include "gmsm_decompress.h"
 #include "gmsm_fft.h"
+#include "gmsm_poly.h"
 
 namespace gmsm {
 

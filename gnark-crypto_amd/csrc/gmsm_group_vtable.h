@@ -214,11 +214,100 @@ struct VTableOf {
                                 int nthreads, uint64_t *out) {
         G::generate_points(base, k0, k1, klimbs, n, nthreads, out);
     }
+    // ---- KZG opening (gmsm_poly.h)
+    using PF = PolyField<typename G::FrP>;
+    using Fr = Fp<typename G::FrP>;
+    static_assert(sizeof(Fr) == G::SCALAR_BYTES, "fr.Element layout");
+    // the k polynomials on the device: host ones are staged in ws.h2d_scalars, device ones are read where they are, after
+    // the work queued on the caller's stream
+    static int poly_input(Workspace &ws, const uint64_t *polys, const void *d_polys, size_t total, hipStream_t caller, const Fr **out) {
+        int rc;
+        if (polys) {
+            if ((rc = ws.h2d_scalars.ensure(total * sizeof(Fr)))) return rc;
+            HIP_TRY(hipMemcpyAsync(ws.h2d_scalars.ptr, polys, total * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+            *out = (const Fr *)ws.h2d_scalars.ptr;
+            return GMSM_OK;
+        }
+        if ((rc = order_after(ws, caller))) return rc;
+        *out = (const Fr *)d_polys;
+        return GMSM_OK;
+    }
+    static size_t poly_scratch(const size_t *lens, size_t k) {
+        size_t s = 0;
+        for (size_t i = 0; i < k; ++i) s = std::max(s, PF::scratch_elems(lens[i]));
+        return s;
+    }
+    static int poly_eval(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
+                         hipStream_t caller, uint64_t *out_values) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        size_t total = 0;
+        for (size_t i = 0; i < k; ++i) total += lens[i];
+        const Fr *in;
+        int rc = poly_input(ws, polys, d_polys, total, caller, &in);
+        if (rc) return rc;
+        if ((rc = ws.poly.ensure((k + poly_scratch(lens, k)) * sizeof(Fr)))) return rc;
+        Fr *vals = (Fr *)ws.poly.ptr, *scratch = vals + k;
+        const FftPowers<typename G::FrP> pw = PF::powers_of(point);
+        for (size_t i = 0, off = 0; i < k; off += lens[i], ++i)
+            if ((rc = PF::suffix(ws.stream, pw, in + off, lens[i], nullptr, vals + i, scratch))) return rc;
+        HIP_TRY(hipMemcpyAsync(out_values, vals, k * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    static int poly_div(Context &ctx, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point, hipStream_t caller,
+                        uint64_t *out_h, void *d_out_h, uint64_t *out_value) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const Fr *in;
+        int rc = poly_input(ws, poly, d_poly, n, caller, &in);
+        if (rc) return rc;
+        if (d_out_h && poly && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out_h
+        const size_t hbuf = out_h ? n - 1 : 0;
+        if ((rc = ws.poly.ensure((1 + hbuf + PF::scratch_elems(n)) * sizeof(Fr)))) return rc;
+        Fr *value = (Fr *)ws.poly.ptr, *h = out_h ? value + 1 : (Fr *)d_out_h, *scratch = value + 1 + hbuf;
+        if ((rc = PF::suffix(ws.stream, PF::powers_of(point), in, n, n > 1 ? h : nullptr, value, scratch))) return rc;
+        if (out_h && n > 1) HIP_TRY(hipMemcpyAsync(out_h, h, (n - 1) * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        if (out_value) HIP_TRY(hipMemcpyAsync(out_value, value, sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    static int kzg_open(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
+                        const uint64_t *gamma, hipStream_t caller, uint64_t *out_claimed, uint64_t *out_jac, const ResidentBases *resident) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        size_t total = 0, maxlen = 0;
+        for (size_t i = 0; i < k; ++i) total += lens[i], maxlen = std::max(maxlen, lens[i]);
+        const Fr *in;
+        int rc = poly_input(ws, polys, d_polys, total, caller, &in);
+        if (rc) return rc;
+        const bool folds = k > 1;
+        const size_t ol_elems = folds ? (2 * k * 8 + sizeof(Fr) - 1) / sizeof(Fr) : 0;
+        const size_t elems = 1 + (maxlen - 1) + (folds ? maxlen : 0) + ol_elems + PF::scratch_elems(maxlen);
+        if ((rc = ws.poly.ensure(elems * sizeof(Fr)))) return rc;
+        Fr *value = (Fr *)ws.poly.ptr, *h = value + 1, *folded = h + (maxlen - 1);
+        uint64_t *off_len = (uint64_t *)(folded + (folds ? maxlen : 0));
+        Fr *scratch = folded + (folds ? maxlen : 0) + ol_elems;
+        const Fr *v = in;
+        if (folds) {
+            if ((rc = PF::fold(ws.stream, in, lens, k, maxlen, gamma, off_len, folded))) return rc;
+            v = folded;
+        }
+        if ((rc = PF::suffix(ws.stream, PF::powers_of(point), v, maxlen, h, value, scratch))) return rc;
+        if (out_claimed) HIP_TRY(hipMemcpyAsync(out_claimed, value, sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        // the quotient is committed where it is: the resident MultiExp over the first maxlen - 1 bases
+        typename G::J j;
+        if ((rc = G::multiexp_device(ctx, ws, nullptr, h, maxlen - 1, ws.stream, &j, resident))) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        memcpy(out_jac, &j, sizeof j);
+        return GMSM_OK;
+    }
     static const GroupVTable *get() {
         static const GroupVTable vt = {G::FR_BITS,      G::AFF_BYTES,   G::SCALAR_BYTES, sizeof(typename G::J),
                                        sizeof(typename G::Ext), &multiexp_host, &multiexp_device, &window_sums,
                                        &fold,           &jac_to_affine, &debug_decompose, &debug_field_op,
-                                       &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info};
+                                       &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info,
+                                       &poly_eval, &poly_div, &kzg_open};
         return &vt;
     }
 };

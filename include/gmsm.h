@@ -269,6 +269,33 @@ int gmsm_fft_domain_info(uint64_t handle, uint64_t *cardinality, uint64_t *gener
 int gmsm_fft(uint64_t handle, uint64_t *a, void *d_a, size_t n, int inverse, int decimation, int on_coset, void *hip_stream);
 int gmsm_fft_bit_reverse(int group, uint64_t *a, void *d_a, size_t n, void *hip_stream);
 
+/* ---- KZG opening (ecc/<curve>/kzg/kzg.go): the host arithmetic of Open and BatchOpenSinglePoint on the device, over the
+ *      scalar field of `group`'s curve; results are bit-identical to the reference's (canonical Montgomery fr.Element).
+ *      Polynomials are fr.Element coefficient vectors, lowest degree first; k of them are concatenated (lens[i]
+ *      coefficients each), given as exactly one of a host pointer / a device pointer (16-byte aligned, produced on
+ *      hip_stream). Inputs are never modified. Every call returns when its results are complete; scratch comes from the
+ *      workspace of the call (gmsm_trim gives it back).
+ *   gmsm_poly_eval: out_values[i] = f_i(point), Horner (eval, kzg.go:55-63); an empty polynomial is GMSM_ERR_ARG.
+ *   gmsm_poly_div_x_minus_a: dividePolyByXminusA (kzg.go:565-583): h = (f - f(a)) / (X - a), n - 1 coefficients to exactly
+ *      one of out_h (host) / d_out_h (device), and f(a) to out_value (may be NULL). n == 1: f(a) and an empty quotient;
+ *      n == 0 is GMSM_ERR_ARG.
+ *   gmsm_kzg_open: kzg.Open over registered bases (gmsm_bases_register*): out_claimed = f(point), out_h_jac =
+ *      Commit(dividePolyByXminusA(f)) as Jacobian {X,Y,Z}. The quotient stays in HBM and goes through the resident MultiExp
+ *      (window tables included when the handle has them).
+ *   gmsm_kzg_open_folded: BatchOpenSinglePoint after the Fiat-Shamir challenge gamma (deriveGamma stays with the caller):
+ *      out_h_jac = Commit((sum_i gamma^i f_i - sum_i gamma^i f_i(a)) / (X - a)), f_i zero beyond lens[i] (kzg.go:302-326).
+ *   Errors as the reference: n == 0, n == 1 (the empty quotient, which Commit refuses), n > the registered size, and in the
+ *   batch entry any empty member or a largest member of length 1, are GMSM_ERR_ARG with the text
+ *   "invalid polynomial size (larger than SRS or == 0)". ---- */
+int gmsm_poly_eval(int group, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
+                   void *hip_stream, uint64_t *out_values);
+int gmsm_poly_div_x_minus_a(int group, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point,
+                            void *hip_stream, uint64_t *out_h, void *d_out_h, uint64_t *out_value);
+int gmsm_kzg_open(uint64_t handle, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point,
+                  void *hip_stream, uint64_t *out_claimed, uint64_t *out_h_jac);
+int gmsm_kzg_open_folded(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                         const uint64_t *point, const uint64_t *gamma, void *hip_stream, uint64_t *out_h_jac);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals

@@ -5,6 +5,7 @@
 package kzg
 
 import (
+	"hash"
 	"io"
 	"os"
 
@@ -71,6 +72,16 @@ func (rk *ResidentProvingKey) CommitBatch(ps [][]fr.Element) ([]Digest, error) {
 		out[i] = d
 	}
 	return out, nil
+}
+
+// Open is Open(p, point, pk) (kzg.go:180-205).
+func (rk *ResidentProvingKey) Open(p []fr.Element, point fr.Element) (OpeningProof, error) {
+	return Open(p, point, rk.host)
+}
+
+// BatchOpenSinglePoint is BatchOpenSinglePoint(polynomials, digests, point, hf, pk, dataTranscript...) (kzg.go:246-339).
+func (rk *ResidentProvingKey) BatchOpenSinglePoint(polynomials [][]fr.Element, digests []Digest, point fr.Element, hf hash.Hash, dataTranscript ...[]byte) (BatchOpeningProof, error) {
+	return BatchOpenSinglePoint(polynomials, digests, point, hf, rk.host, dataTranscript...)
 }
 
 // Release does nothing in this build.

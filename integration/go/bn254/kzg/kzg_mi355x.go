@@ -7,7 +7,7 @@
 //	Commit(p, pk)                       kzg.go:159-176  (res.MultiExp(pk.G1[:len(p)], p, config))
 //	Open / BatchOpenSinglePoint         kzg.go:180, :246 (Commit of the quotient)
 //
-// unchanged. This file adds a type next to ProvingKey and touches nothing of the reference (kzg_purego.go gives the same API
+// unchanged; the methods of the same names below do their host arithmetic on the device as well. This file adds a type next to ProvingKey and touches nothing of the reference (kzg_purego.go gives the same API
 // over the plain ProvingKey for builds without the tag, so callers compile either way):
 //
 //	NewResidentProvingKey(pk, tables)   gmsm_bases_register (+ gmsm_bases_precompute: window tables, one bucket set per commitment)
@@ -21,6 +21,10 @@
 //	                                    gmsm_bases_register_raw. subgroupCheck = false is UnsafeReadFrom (:151-158)
 //	(*ResidentProvingKey).Commit        gmsm_multiexp_bases; below MinDevicePoints the package's Commit when the host copy exists
 //	(*ResidentProvingKey).CommitBatch   k polynomials of equal length in one call, two MSMs in flight (gmsm_multiexp_bases_batch)
+//	(*ResidentProvingKey).Open          kzg.Open: eval + dividePolyByXminusA as a parallel suffix scan on the device, the quotient
+//	                                    committed where it is (gmsm_kzg_open)
+//	(*ResidentProvingKey).BatchOpenSinglePoint  the claimed values on the device (gmsm_poly_eval), deriveGamma on the host, then
+//	                                    the gamma fold, the division and the commitment on the device (gmsm_kzg_open_folded)
 //	(*ResidentProvingKey).Release       gmsm_bases_release (also the finalizer)
 //
 // NOT compiled in the build environment of this repository (no Go toolchain there); the C entry points it calls are covered
@@ -38,6 +42,7 @@ import "C"
 import (
 	"encoding/binary"
 	"errors"
+	"hash"
 	"io"
 	"os"
 	"runtime"
@@ -241,6 +246,84 @@ func (rk *ResidentProvingKey) CommitBatch(ps [][]fr.Element) ([]Digest, error) {
 	}
 	runtime.KeepAlive(rk)
 	return bn254.BatchJacobianToAffineG1(jacs), nil
+}
+
+// Open is Open(p, point, pk) (kzg.go:180-205) over the resident SRS: the claimed value eval(p, point) and the quotient
+// dividePolyByXminusA(_p, ClaimedValue, point) are computed on the device and the quotient is committed there
+// (gmsm_kzg_open) - it never exists on the host. Below MinDevicePoints the package's Open when the host copy exists.
+func (rk *ResidentProvingKey) Open(p []fr.Element, point fr.Element) (OpeningProof, error) {
+	if len(p) == 0 || len(p) > rk.n {
+		return OpeningProof{}, ErrInvalidPolynomialSize
+	}
+	if len(p) < MinDevicePoints && len(rk.host.G1) >= len(p) {
+		return Open(p, point, rk.host)
+	}
+	if len(p) == 1 { // Commit of the empty quotient refuses it (kzg.go:197)
+		return OpeningProof{}, ErrInvalidPolynomialSize
+	}
+	var res OpeningProof
+	var jac bn254.G1Jac
+	if rc := C.gmsm_kzg_open(rk.handle, (*C.uint64_t)(unsafe.Pointer(&p[0])), nil, C.size_t(len(p)), (*C.uint64_t)(unsafe.Pointer(&point)), nil,
+		(*C.uint64_t)(unsafe.Pointer(&res.ClaimedValue)), (*C.uint64_t)(unsafe.Pointer(&jac))); rc != 0 {
+		return OpeningProof{}, gmsmErr()
+	}
+	res.H.FromJacobian(&jac)
+	runtime.KeepAlive(rk)
+	return res, nil
+}
+
+// BatchOpenSinglePoint is BatchOpenSinglePoint(polynomials, digests, point, hf, pk, dataTranscript...) (kzg.go:246-339) over
+// the resident SRS: the claimed values come from the device (gmsm_poly_eval), the challenge gamma from the package's own
+// deriveGamma, and the fold sum_i gamma^i f_i, its quotient by (X - point) and the commitment to it run on the device
+// (gmsm_kzg_open_folded). The folded evaluation sum_i gamma^i f_i(point) of kzg.go:287-297 is not formed: the reference
+// subtracts it from the constant coefficient, which the division then drops, so H does not depend on it.
+func (rk *ResidentProvingKey) BatchOpenSinglePoint(polynomials [][]fr.Element, digests []Digest, point fr.Element, hf hash.Hash, dataTranscript ...[]byte) (BatchOpeningProof, error) {
+	if len(digests) != len(polynomials) {
+		return BatchOpeningProof{}, ErrInvalidNbDigests
+	}
+	largestPoly := -1
+	for _, p := range polynomials {
+		if len(p) == 0 || len(p) > rk.n {
+			return BatchOpeningProof{}, ErrInvalidPolynomialSize
+		}
+		if len(p) > largestPoly {
+			largestPoly = len(p)
+		}
+	}
+	if len(polynomials) > 0 && largestPoly < MinDevicePoints && len(rk.host.G1) >= largestPoly {
+		return BatchOpenSinglePoint(polynomials, digests, point, hf, rk.host, dataTranscript...)
+	}
+	if largestPoly < 2 { // Commit of the empty quotient refuses it (kzg.go:326)
+		return BatchOpeningProof{}, ErrInvalidPolynomialSize
+	}
+	lens := make([]C.size_t, len(polynomials))
+	total := 0
+	for i, p := range polynomials {
+		lens[i] = C.size_t(len(p))
+		total += len(p)
+	}
+	flat := make([]fr.Element, 0, total)
+	for _, p := range polynomials {
+		flat = append(flat, p...)
+	}
+	var res BatchOpeningProof
+	res.ClaimedValues = make([]fr.Element, len(polynomials))
+	if rc := C.gmsm_poly_eval(C.GMSM_BN254_G1, (*C.uint64_t)(unsafe.Pointer(&flat[0])), nil, &lens[0], C.size_t(len(lens)),
+		(*C.uint64_t)(unsafe.Pointer(&point)), nil, (*C.uint64_t)(unsafe.Pointer(&res.ClaimedValues[0]))); rc != 0 {
+		return BatchOpeningProof{}, gmsmErr()
+	}
+	gamma, err := deriveGamma(point, digests, res.ClaimedValues, hf, dataTranscript...)
+	if err != nil {
+		return BatchOpeningProof{}, err
+	}
+	var jac bn254.G1Jac
+	if rc := C.gmsm_kzg_open_folded(rk.handle, (*C.uint64_t)(unsafe.Pointer(&flat[0])), nil, &lens[0], C.size_t(len(lens)),
+		(*C.uint64_t)(unsafe.Pointer(&point)), (*C.uint64_t)(unsafe.Pointer(&gamma)), nil, (*C.uint64_t)(unsafe.Pointer(&jac))); rc != 0 {
+		return BatchOpeningProof{}, gmsmErr()
+	}
+	res.H.FromJacobian(&jac)
+	runtime.KeepAlive(rk)
+	return res, nil
 }
 
 // Release gives the device memory of the key back (gmsm_bases_release); calls that are still running keep their own reference.
