@@ -180,6 +180,7 @@ struct Workspace {
     DeviceBuffer h2d_points, h2d_scalars;  // staging of the host-pointer entries
     DeviceBuffer raw_bytes, flagword;      // point ingest: wire-format bytes, first-offender word
     DeviceBuffer poly;                     // KZG opening (gmsm_poly.h): folded polynomial, quotient, lane and tile carries
+    DeviceBuffer lagrange;                 // ToLagrangeG1 (gmsm_group_fft.h): records, GLV walk table, twiddles
     bool busy = false;  // leased to a call (Context::acquire / release)
     bool ticket = false;  // ... by gmsm_multiexp_bases_submit: only gmsm_multiexp_collect ends that lease
     // state of a submitted, not yet collected call
@@ -199,7 +200,7 @@ struct Workspace {
     size_t trim(size_t keep) {
         DeviceBuffer *all[] = {&upoints, &skip, &seg_lvl, &seg_partials, &seg_flags, &seg_bucket, &parted, &heavy, &long_pieces, &small_sums, &small_done, &digits, &sorted,
                                &blockhist, &counts, &starts, &buckets, &partials, &totals, &red_pre, &carry, &h2d_points,
-                               &h2d_scalars, &raw_bytes, &flagword, &poly};
+                               &h2d_scalars, &raw_bytes, &flagword, &poly, &lagrange};
         size_t freed = 0;
         for (DeviceBuffer *b : all)
             if (b->cap > keep) freed += b->release();
@@ -698,6 +699,12 @@ struct GroupVTable {
     // H = MultiExp(resident[:maxlen - 1], (sum_i gamma^i f_i) / (X - point)); gamma == nullptr: k == 1, no fold
     int (*kzg_open)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
                     const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed, uint64_t *out_jac, const ResidentBases *resident);
+    // ToLagrangeG1 (gmsm_group_fft.h) of n = 2^log2n points, log2n <= fr_max_order: the input is host `coeffs`, device
+    // `d_coeffs` or the first n bases of `from`; the output goes to host `out_affine`, device `d_out_affine` or a new
+    // registration `out_bases`. nullptr for the G2 groups.
+    int (*to_lagrange)(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
+                       hipStream_t stream, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases);
+    unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 
 }  // namespace gmsm

@@ -1418,6 +1418,63 @@ GMSM_EXPORT int gmsm_kzg_open_folded(uint64_t handle, const uint64_t *polys, con
     return kzg_open_impl("gmsm_kzg_open_folded", handle, polys, d_polys, lens, k, point, gamma, hip_stream, nullptr, out_h_jac);
 }
 
+// ------------------------------------------------------------------ ToLagrangeG1 (gmsm_group_fft.h)
+static const char *const ERR_POW2 = "len(coeffs) must be a power of 2";  // ToLagrangeG1, kzg/utils.go
+static const char *const ERR_G1_ONLY = "ToLagrangeG1 is defined for G1 only";
+static const char *const ERR_ROOT = "m is too big: the required root of unity does not exist";  // as gmsm_fft_domain_new
+
+// the size checks of ToLagrangeG1 and computeTwiddlesInv (fr.Generator): no device needed
+static int lagrange_size(const GroupVTable *vt, size_t n, unsigned *log2n) {
+    if (n == 0 || (n & (n - 1))) return fail(GMSM_ERR_ARG, ERR_POW2);
+    unsigned l = 0;
+    while (((size_t)1 << l) < n) ++l;
+    if (l > vt->fr_max_order) return fail(GMSM_ERR_ARG, ERR_ROOT);
+    *log2n = l;
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_to_lagrange_g1(int group, const uint64_t *coeffs, const void *d_coeffs, size_t n, void *hip_stream,
+                                    uint64_t *out_affine, void *d_out_affine) {
+    VT_OR_FAIL(group);
+    const char *E = "gmsm_to_lagrange_g1";
+    if (!vt->to_lagrange) return fail(GMSM_ERR_ARG, ERR_G1_ONLY);
+    unsigned log2n;
+    int rc = lagrange_size(vt, n, &log2n);
+    if (rc) return rc;
+    if ((coeffs == nullptr) == (d_coeffs == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of coeffs (host) / d_coeffs (device)");
+    if ((out_affine == nullptr) == (d_out_affine == nullptr))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_affine (host) / d_out_affine (device)");
+    Context *ctx;
+    if ((rc = get_context_of_pointer(d_coeffs ? d_coeffs : d_out_affine, &ctx))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_coeffs", d_coeffs, ctx->device)) || (rc = check_device_vector(E, "d_out_affine", d_out_affine, ctx->device)))
+        return rc;
+    return vt->to_lagrange(*ctx, coeffs, d_coeffs, nullptr, log2n, (hipStream_t)hip_stream, out_affine, d_out_affine, nullptr);
+}
+
+GMSM_EXPORT int gmsm_bases_to_lagrange(uint64_t handle, size_t n, uint64_t *out_handle) {
+    if (!out_handle) return fail(GMSM_ERR_ARG, "gmsm_bases_to_lagrange: out_handle is null");
+    BasesRef rb = lookup_bases(handle);
+    if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
+    const GroupVTable *vt = vtable(rb->group);
+    if (!vt->to_lagrange) return fail(GMSM_ERR_ARG, ERR_G1_ONLY);
+    unsigned log2n;
+    int rc = lagrange_size(vt, n, &log2n);
+    if (rc) return rc;
+    if (n > rb->n) return fail(GMSM_ERR_ARG, "gmsm_bases_to_lagrange: n is larger than the registered bases");
+    Context *ctx;
+    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
+    HIP_TRY(hipSetDevice(ctx->device));
+    BasesRef out = std::make_shared<ResidentBases>();
+    out->group = rb->group;
+    out->device = ctx->device;
+    if ((rc = vt->to_lagrange(*ctx, nullptr, nullptr, rb.get(), log2n, nullptr, nullptr, nullptr, out.get()))) return rc;
+    std::lock_guard<std::mutex> lk(g_bases_mu);
+    g_bases.push_back(out);
+    *out_handle = g_bases.size();
+    return GMSM_OK;
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {

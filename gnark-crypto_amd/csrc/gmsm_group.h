@@ -20,6 +20,7 @@
 #include "gmsm_decompress.h"
 #include "gmsm_fft.h"
 #include "gmsm_poly.h"
+#include "gmsm_group_fft.h"
 
 namespace gmsm {
 
@@ -818,6 +819,51 @@ struct Group : GroupHost<F_, FrP_> {
         if ((rc = ws.buckets.ensure(n * sizeof(XYZZL<U>)))) return rc;
         hipLaunchKernelGGL((k_jac_to_recs<U, INLINE_OPS>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ws.stream, d_jac, n,
                            ws.buckets.ptr);
+        HIP_TRY(hipGetLastError());
+        return normalize_records(ws, n, d_out);
+    }
+
+    // ToLagrangeG1 (gmsm_group_fft.h): n = 2^log2n points at d_in - Go-layout affine, or the packed lazy form of registered
+    // bases (`packed`) - to d_out, Go-layout affine; d_out may be d_in. Scratch: ws.lagrange (records, the GLV walk's table,
+    // the twiddles), ws.buckets (the bit-reversed records), ws.partials (the normalisation's prefix products).
+    static constexpr bool LAGRANGE_GLV = GMSM_LAGRANGE_GLV != 0;
+    static int to_lagrange(Workspace &ws, const void *d_in, bool packed, unsigned log2n, void *d_out) {
+        static_assert(std::is_same<U, FpU<typename LzTraits<U>::Params>>::value, "ToLagrangeG1: coordinates in Fp");
+        using Tw = LagTw<FrP, LAGRANGE_GLV>;
+        using Fld = FftField<FrP>;
+        using Fr = Fp<FrP>;
+        constexpr size_t REC = sizeof(XYZZL<U>);
+        const size_t n = (size_t)1 << log2n, half = n / 2;
+        const size_t tab_recs = LAGRANGE_GLV ? 3 * n : 0;  // 3 slots per thread of the widest stage (stage 0: n)
+        const size_t tw_off = (n + tab_recs) * REC;
+        int rc;
+        if ((rc = ws.lagrange.ensure(tw_off + (n + 1) * sizeof(Tw)))) return rc;
+        if ((rc = ws.buckets.ensure(n * REC))) return rc;
+        char *recs = (char *)ws.lagrange.ptr, *tab = recs + n * REC;
+        Tw *tw = (Tw *)(recs + tw_off);
+        // buffers: stage 0 runs out of place, the later stages in place, the last one into ws.buckets (the normalisation's
+        // input). n = 1: the load alone; n = 2: recs -> buckets; else buckets -> recs -> ... -> recs -> buckets.
+        void *const buckets = ws.buckets.ptr;
+        void *loaded = log2n == 1 ? (void *)recs : buckets;
+        if (packed)
+            hipLaunchKernelGGL((k_group_fft_load<U, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ws.stream, d_in, n, loaded);
+        else
+            hipLaunchKernelGGL((k_group_fft_load<U, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ws.stream, d_in, n, loaded);
+        if (log2n) {
+            // w = fr.Generator(n) (as FftField::domain_new), twiddles of w^-1 (computeTwiddlesInv), 1/n
+            const Fr w = Fld::pow2k(Fld::from_words(FrP::ROOT_OF_UNITY), FrP::MAX_ORDER - log2n);
+            Fr card = Fr::one();
+            for (unsigned i = 0; i < log2n; ++i) card = fp_dbl(card);
+            hipLaunchKernelGGL((k_group_fft_twiddles<FrP, LAGRANGE_GLV>), dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, ws.stream,
+                               Fld::powers_of(fp_inv(w)), fp_inv(card), half, tw);
+            for (unsigned s = 0; s < log2n; ++s) {
+                const void *src = s == 0 ? loaded : (const void *)recs;
+                void *dst = s + 1 == log2n ? buckets : (void *)recs;
+                hipLaunchKernelGGL((k_group_fft_stage<typename LzTraits<U>::Params, Consts, FrP, LAGRANGE_GLV, INLINE_OPS>),
+                                   dim3((unsigned)(((s ? half : n) + 255) / 256)), dim3(256), 0, ws.stream, src, dst, log2n, s,
+                                   (const Tw *)tw, (void *)tab);
+            }
+        }
         HIP_TRY(hipGetLastError());
         return normalize_records(ws, n, d_out);
     }

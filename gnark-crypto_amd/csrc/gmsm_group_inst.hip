@@ -27,6 +27,6 @@ using TheGroup = Group<Fp<bw6_761_fp_params>, bw6_761_g2_fr_params, bw6_761_g2_c
 #error "GMSM_GROUP_ID must be 0..5"
 #endif
 
-const GroupVTable *GMSM_VT_NAME() { return VTableOf<TheGroup>::get(); }
+const GroupVTable *GMSM_VT_NAME() { return VTableOf<TheGroup, (GMSM_GROUP_ID % 2 == 0)>::get(); }  // even ids: G1
 
 }  // namespace gmsm

@@ -8,7 +8,7 @@ namespace gmsm {
 
 // ------------------------------------------------------------------ function table
 
-template <class G>
+template <class G, bool IS_G1>
 struct VTableOf {
     static int multiexp_host(const uint64_t *points, size_t n_points, const uint64_t *scalars, size_t n_scalars,
                              int nb_tasks, uint64_t *out_jac) {
@@ -302,12 +302,43 @@ struct VTableOf {
         memcpy(out_jac, &j, sizeof j);
         return GMSM_OK;
     }
+    // ---- ToLagrangeG1 (gmsm_group_fft.h)
+    static int to_lagrange(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
+                           hipStream_t caller, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const size_t n = (size_t)1 << log2n, bytes = n * G::AFF_BYTES;
+        int rc;
+        const void *src = d_coeffs;
+        if (coeffs) {
+            if ((rc = ws.h2d_points.ensure(bytes))) return rc;
+            HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, coeffs, bytes, hipMemcpyHostToDevice, ws.stream));
+            src = ws.h2d_points.ptr;
+        } else if (from) {
+            src = from->upoints.ptr;
+        }
+        if ((d_coeffs || d_out_affine) && (rc = order_after(ws, caller))) return rc;  // the caller's stream owns those vectors
+        void *dst = d_out_affine;
+        if (!dst) {  // host output or a new registration: staged in h2d_points (the load has read any host input by then)
+            if ((rc = ws.h2d_points.ensure(bytes))) return rc;
+            dst = ws.h2d_points.ptr;
+        }
+        if ((rc = G::to_lagrange(ws, src, from != nullptr, log2n, dst))) return rc;
+        if (out_affine) HIP_TRY(hipMemcpyAsync(out_affine, dst, bytes, hipMemcpyDeviceToHost, ws.stream));
+        if (out_bases && (rc = G::register_bases(ctx, dst, n, ws.stream, out_bases))) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    static constexpr decltype(GroupVTable::to_lagrange) lagrange_entry() {
+        if constexpr (IS_G1) return &to_lagrange;
+        else return nullptr;
+    }
     static const GroupVTable *get() {
         static const GroupVTable vt = {G::FR_BITS,      G::AFF_BYTES,   G::SCALAR_BYTES, sizeof(typename G::J),
                                        sizeof(typename G::Ext), &multiexp_host, &multiexp_device, &window_sums,
                                        &fold,           &jac_to_affine, &debug_decompose, &debug_field_op,
                                        &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info,
-                                       &poly_eval, &poly_div, &kzg_open};
+                                       &poly_eval, &poly_div, &kzg_open, lagrange_entry(), (unsigned)G::FrP::MAX_ORDER};
         return &vt;
     }
 };

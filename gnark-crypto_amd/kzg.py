@@ -7,6 +7,7 @@ Keeps the reference's names and meaning (ecc/bn254/kzg/kzg.go):
     values, H = BatchOpenSinglePoint(polys, point, gamma, rb)  # BatchOpenSinglePoint (kzg.go:246-339) after the challenge
     values = PolyEval(curve, polys, point)                     # eval (kzg.go:55-63) of each polynomial
     h, value = DividePolyByXMinusA(curve, p, point)            # dividePolyByXminusA (kzg.go:565-583) and f(point)
+    lagrange = ToLagrangeG1(curve, srs_g1)                     # ToLagrangeG1 (utils.go:25-64): the SRS in Lagrange form
 
 Polynomials and field elements are numpy uint64 arrays in the layout of []fr.Element (Montgomery limbs), lowest degree
 first; H is the affine commitment (G1Affine limbs). Inputs are never modified. Errors raise ValueError with the
@@ -148,3 +149,22 @@ def batch_open_device(d_polys, lens, point, gamma, rb, stream=0):
     _check(_lib.load().gmsm_kzg_open_folded(rb.handle, None, d_polys, clens, len(lens), _ptr(point), _ptr(gamma),
                                             stream or None, _ptr(jac)))
     return poly_eval_device(g.curve, d_polys, lens, point, stream), _affine(rb, jac)
+
+
+ERR_POW2 = "len(coeffs) must be a power of 2"  # ToLagrangeG1, kzg/utils.go
+
+
+def ToLagrangeG1(curve, points):
+    """kzg.ToLagrangeG1 (utils.go:25-64) on the device: (n, 2 fp_limbs) affine G1 limbs in, the same shape out, with
+    out[i] = (1/n) sum_j w^(-ij) points[j] - for an SRS [tau^j]G that is [L_i(tau)]G. n must be a power of two; inputs
+    must lie in the r-torsion (as for the reference's mulGLV). Errors raise ValueError with the reference's text."""
+    c = _curve(curve)
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 2 * c.fp_limbs)
+    out = np.zeros_like(pts)
+    _check(_lib.load().gmsm_to_lagrange_g1(_gid(c), _host_or_none(pts), None, pts.shape[0], None, _host_or_none(out), None))
+    return out
+
+
+def to_lagrange_device(curve, d_in, n, d_out, stream=0):
+    """ToLagrangeG1 from device pointer d_in (n affine points, produced on `stream`) to d_out (may equal d_in)."""
+    _check(_lib.load().gmsm_to_lagrange_g1(_gid(curve), None, d_in, int(n), stream or None, None, d_out))

@@ -434,6 +434,16 @@ class ResidentBases:
     def table_bits(self):
         return int(_lib.load().gmsm_bases_table_bits(self.handle))
 
+    def to_lagrange(self, n=None):
+        """gmsm_bases_to_lagrange: ToLagrangeG1 of the first n bases (default: all), computed on the device from the resident
+        points and registered as a new ResidentBases. Errors raise ValueError with the library's text."""
+        L = _lib.load()
+        n = self.n if n is None else int(n)
+        handle = _lib.ctypes.c_uint64(0)
+        if L.gmsm_bases_to_lagrange(self.handle, n, _lib.ctypes.byref(handle)):
+            raise ValueError(_lib.last_error())
+        return ResidentBases(self.group, handle.value, n)
+
     def MultiExp(self, scalars, config=MultiExpConfig()):
         """MultiExp(bases[:len(scalars)], scalars): returns (jacobian_limbs, None) or (None, error)."""
         L = _lib.load()

@@ -296,6 +296,24 @@ int gmsm_kzg_open(uint64_t handle, const uint64_t *poly, const void *d_poly, siz
 int gmsm_kzg_open_folded(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
                          const uint64_t *point, const uint64_t *gamma, void *hip_stream, uint64_t *out_h_jac);
 
+/* ---- ToLagrangeG1 (ecc/<curve>/kzg/utils.go:25-64): the Lagrange form of an SRS, out[i] = (1/n) sum_j w^(-ij) P_j with
+ *      w = fr.Generator(n) - for P_j = [tau^j]G that is [L_i(tau)]G - as an inverse FFT over G1 points on the device
+ *      (gmsm_group_fft.h). Results are canonical affine limbs (infinity = (0, 0)), bit-identical to the reference's.
+ *      G1 groups only: a G2 id is GMSM_ERR_ARG "ToLagrangeG1 is defined for G1 only".
+ *   Precondition (as the reference's ScalarMultiplication, mulGLV): every input point lies in the r-torsion; the twiddle
+ *      products use the GLV endomorphism (see GMSM_OPT_GLV).
+ *   gmsm_to_lagrange_g1: n points in from exactly one of coeffs (host) / d_coeffs (device, 16-byte aligned, produced on
+ *      hip_stream), out to exactly one of out_affine / d_out_affine; the output may alias the input. n = 1 returns the
+ *      point unchanged (canonical). n == 0 or not a power of two: GMSM_ERR_ARG "len(coeffs) must be a power of 2"; n beyond
+ *      the scalar field's 2-adicity: GMSM_ERR_ARG "m is too big: the required root of unity does not exist".
+ *   gmsm_bases_to_lagrange: the Lagrange form of the first n bases of a registered handle (gmsm_bases_register*), computed
+ *      from the resident points without a host round trip and registered as a NEW handle (an ordinary one:
+ *      gmsm_bases_precompute, gmsm_multiexp_bases*, gmsm_bases_release). n larger than the handle's size, or an unknown
+ *      handle: GMSM_ERR_ARG. Both calls return when the result is complete; scratch comes from the call's workspace. ---- */
+int gmsm_to_lagrange_g1(int group, const uint64_t *coeffs, const void *d_coeffs, size_t n, void *hip_stream,
+                        uint64_t *out_affine, void *d_out_affine);
+int gmsm_bases_to_lagrange(uint64_t handle, size_t n, uint64_t *out_handle);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals

@@ -25,6 +25,8 @@
 //	                                    committed where it is (gmsm_kzg_open)
 //	(*ResidentProvingKey).BatchOpenSinglePoint  the claimed values on the device (gmsm_poly_eval), deriveGamma on the host, then
 //	                                    the gamma fold, the division and the commitment on the device (gmsm_kzg_open_folded)
+//	(*ResidentProvingKey).ToLagrange    ToLagrangeG1(pk.G1[:size]) (utils.go:25-64) on the device, from the resident points to a
+//	                                    new resident key (gmsm_bases_to_lagrange); ToLagrangeG1Resident: the same from host points
 //	(*ResidentProvingKey).Release       gmsm_bases_release (also the finalizer)
 //
 // NOT compiled in the build environment of this repository (no Go toolchain there); the C entry points it calls are covered
@@ -44,6 +46,7 @@ import (
 	"errors"
 	"hash"
 	"io"
+	"math/bits"
 	"os"
 	"runtime"
 	"unsafe"
@@ -324,6 +327,43 @@ func (rk *ResidentProvingKey) BatchOpenSinglePoint(polynomials [][]fr.Element, d
 	res.H.FromJacobian(&jac)
 	runtime.KeepAlive(rk)
 	return res, nil
+}
+
+// errNotPowerOfTwo is ToLagrangeG1's error for a length that is not a power of two (utils.go:26-28).
+var errNotPowerOfTwo = errors.New("len(coeffs) must be a power of 2")
+
+// ToLagrangeG1Resident is ToLagrangeG1(coeffs) (utils.go:25-64) on the device: the inverse FFT over the points, its
+// twiddle products and the batch normalisation run there (gmsm_to_lagrange_g1), with the reference's bits as result.
+// coeffs must lie in the r-torsion, as for the reference's mulGLV.
+func ToLagrangeG1Resident(coeffs []bls12381.G1Affine) ([]bls12381.G1Affine, error) {
+	if bits.OnesCount64(uint64(len(coeffs))) != 1 {
+		return nil, errNotPowerOfTwo
+	}
+	out := make([]bls12381.G1Affine, len(coeffs))
+	if rc := C.gmsm_to_lagrange_g1(C.GMSM_BLS12_381_G1, (*C.uint64_t)(unsafe.Pointer(&coeffs[0])), nil, C.size_t(len(coeffs)), nil,
+		(*C.uint64_t)(unsafe.Pointer(&out[0])), nil); rc != 0 {
+		return nil, gmsmErr()
+	}
+	return out, nil
+}
+
+// ToLagrange returns the Lagrange form of the first size points of the key, ToLagrangeG1(pk.G1[:size]), as a new resident
+// key: computed from the points in HBM and registered there (gmsm_bases_to_lagrange) - nothing crosses PCIe. The new key
+// has no host copy; Release it (or leave it to the finalizer) like any other.
+func (rk *ResidentProvingKey) ToLagrange(size int) (*ResidentProvingKey, error) {
+	if size < 0 || size > rk.n {
+		return nil, ErrInvalidPolynomialSize
+	}
+	if bits.OnesCount64(uint64(size)) != 1 {
+		return nil, errNotPowerOfTwo
+	}
+	lk := &ResidentProvingKey{n: size}
+	if rc := C.gmsm_bases_to_lagrange(rk.handle, C.size_t(size), &lk.handle); rc != 0 {
+		return nil, gmsmErr()
+	}
+	runtime.SetFinalizer(lk, func(k *ResidentProvingKey) { k.Release() })
+	runtime.KeepAlive(rk)
+	return lk, nil
 }
 
 // Release gives the device memory of the key back (gmsm_bases_release); calls that are still running keep their own reference.

@@ -9,6 +9,7 @@ import (
 	"io"
 	"os"
 
+	"github.com/consensys/gnark-crypto/ecc/bw6-761"
 	"github.com/consensys/gnark-crypto/ecc/bw6-761/fr"
 )
 
@@ -82,6 +83,23 @@ func (rk *ResidentProvingKey) Open(p []fr.Element, point fr.Element) (OpeningPro
 // BatchOpenSinglePoint is BatchOpenSinglePoint(polynomials, digests, point, hf, pk, dataTranscript...) (kzg.go:246-339).
 func (rk *ResidentProvingKey) BatchOpenSinglePoint(polynomials [][]fr.Element, digests []Digest, point fr.Element, hf hash.Hash, dataTranscript ...[]byte) (BatchOpeningProof, error) {
 	return BatchOpenSinglePoint(polynomials, digests, point, hf, rk.host, dataTranscript...)
+}
+
+// ToLagrangeG1Resident is ToLagrangeG1(coeffs) (utils.go:25-64).
+func ToLagrangeG1Resident(coeffs []bw6761.G1Affine) ([]bw6761.G1Affine, error) {
+	return ToLagrangeG1(coeffs)
+}
+
+// ToLagrange returns ToLagrangeG1(pk.G1[:size]) as a new key.
+func (rk *ResidentProvingKey) ToLagrange(size int) (*ResidentProvingKey, error) {
+	if size < 0 || size > len(rk.host.G1) {
+		return nil, ErrInvalidPolynomialSize
+	}
+	lag, err := ToLagrangeG1(rk.host.G1[:size])
+	if err != nil {
+		return nil, err
+	}
+	return &ResidentProvingKey{host: ProvingKey{G1: lag}}, nil
 }
 
 // Release does nothing in this build.
