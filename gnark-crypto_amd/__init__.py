@@ -8,3 +8,4 @@ from .multiexp import G1Affine, G1Jac, G2Affine, G2Jac, MultiExpConfig, get_devi
 from ._lib import options, set_option, get_option, trim, shutdown  # noqa: F401  (gmsm_set_option / gmsm_trim / gmsm_shutdown)
 from . import fft  # noqa: F401  (fr/fft mirror: fft.NewDomain, fft.DIT / fft.DIF, fft.OnCoset, fft.BitReverse)
 from . import kzg  # noqa: F401  (kzg mirror: kzg.Open, kzg.BatchOpenSinglePoint, kzg.PolyEval, kzg.DividePolyByXMinusA, kzg.ToLagrangeG1)
+from . import shplonk  # noqa: F401  (shplonk mirror: shplonk.BatchOpen, shplonk.OpenW, shplonk.OpenWPrime)

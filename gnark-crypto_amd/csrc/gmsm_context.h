@@ -704,6 +704,17 @@ struct GroupVTable {
     // registration `out_bases`. nullptr for the G2 groups.
     int (*to_lagrange)(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
                        hipStream_t stream, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases);
+    // shplonk.BatchOpen over registered G1 bases (gmsm_shplonk.h): polynomials as for kzg_open; `points` holds the sets S_i one
+    // after the other (npoints[i] elements each, host), `claimed` the values in the same layout. nullptr for the G2 groups.
+    //   open_w: out_claimed, w = sum_i gamma^i (f_i div Z_(S_i)) (maxlen elements) to out_w (host) or d_out_w (device), W = Commit(w)
+    //   open_wprime: W' = Commit((sum_i c_i f_i - sum_i c_i r_i(z) - Z_T(z) w) / (X - z)), w from the host or the device
+    int (*shplonk_open_w)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *points,
+                          const size_t *npoints, const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed, uint64_t *out_w,
+                          void *d_out_w, uint64_t *out_jac, const ResidentBases *resident);
+    int (*shplonk_open_wprime)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                               const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
+                               const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t stream, uint64_t *out_jac,
+                               const ResidentBases *resident);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

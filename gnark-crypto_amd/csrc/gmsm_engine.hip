@@ -1418,6 +1418,91 @@ GMSM_EXPORT int gmsm_kzg_open_folded(uint64_t handle, const uint64_t *polys, con
     return kzg_open_impl("gmsm_kzg_open_folded", handle, polys, d_polys, lens, k, point, gamma, hip_stream, nullptr, out_h_jac);
 }
 
+// ------------------------------------------------------------------ shplonk.BatchOpen (gmsm_shplonk.h)
+static const char *const ERR_SHPLONK_G1 = "shplonk opens over G1 bases only";
+
+// The checks both entries share (shplonk.go:44-83 and Commit's size check, kzg.go:159-162), then the device of the bases.
+// maxSizePolys = max(max_i lens[i], max_i npoints[i] + 1); Commit(wPrime) runs over maxSizePolys + sum_i npoints[i] - 1
+// coefficients in the reference, so that many bases must be registered (the device MSMs run over true lengths only).
+static int shplonk_nonempty(const char *E, const size_t *lens, size_t k, const uint64_t *points, const size_t *npoints) {
+    if (k == 0 || !lens || !npoints || !points) return fail(GMSM_ERR_ARG, std::string(E) + ": no polynomial, or lens / points / npoints is null");
+    return GMSM_OK;
+}
+
+static int shplonk_check(const char *E, uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                         const uint64_t *points, const size_t *npoints, BasesRef *rb_out, const GroupVTable **vt_out, Context **ctx_out) {
+    if ((polys == nullptr) == (d_polys == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of polys (host) / d_polys (device)");
+    BasesRef rb = lookup_bases(handle);
+    if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
+    const GroupVTable *vt = vtable(rb->group);
+    if (!vt->shplonk_open_w) return fail(GMSM_ERR_ARG, ERR_SHPLONK_G1);
+    size_t max_size = 0, total_points = 0;
+    for (size_t i = 0; i < k; ++i) {
+        if (lens[i] == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": polynomial " + std::to_string(i) + " is empty (eval reads p[len(p)-1])");
+        if (npoints[i] == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": polynomial " + std::to_string(i) + " has no opening point");
+        max_size = std::max(max_size, std::max(lens[i], npoints[i] + 1));
+        total_points += npoints[i];
+    }
+    // equal points inside one set: the reference's interpolate inverts zero there (shplonk.go:406-415) and returns a
+    // meaningless proof without an error; refused here. Elements are canonical, so equal values have equal limbs.
+    const size_t sb = vt->scalar_bytes;
+    const unsigned char *pt = (const unsigned char *)points;
+    for (size_t i = 0, p = 0; i < k; p += npoints[i], ++i)
+        for (size_t a = 0; a < npoints[i]; ++a)
+            for (size_t b = a + 1; b < npoints[i]; ++b)
+                if (memcmp(pt + (p + a) * sb, pt + (p + b) * sb, sb) == 0)
+                    return fail(GMSM_ERR_ARG, std::string(E) + ": set " + std::to_string(i) + " holds the same point twice (points " +
+                                                  std::to_string(a) + " and " + std::to_string(b) + ")");
+    if (max_size + total_points - 1 > rb->n) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);
+    Context *ctx;
+    int rc = get_context_for(rb->device, &ctx);  // the bases decide the device
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
+    *rb_out = rb, *vt_out = vt, *ctx_out = ctx;
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_shplonk_open_w(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                                    const uint64_t *points, const size_t *npoints, const uint64_t *gamma, void *hip_stream,
+                                    uint64_t *out_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_w_jac) {
+    const char *E = "gmsm_shplonk_open_w";
+    if (int rc0 = shplonk_nonempty(E, lens, k, points, npoints)) return rc0;
+    if (!gamma || !out_claimed || !out_w_jac) return fail(GMSM_ERR_ARG, std::string(E) + ": gamma, out_claimed and out_w_jac must not be null");
+    if ((out_w == nullptr) == (d_out_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_w (host) / d_out_w (device)");
+    if ((polys && (polys == out_w || polys == out_claimed || polys == out_w_jac)) || (d_polys && d_polys == d_out_w) || out_claimed == out_w ||
+        out_claimed == out_w_jac || out_w == out_w_jac || points == out_claimed || points == out_w)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": an output aliases an input or another output (inputs are never modified)");
+    BasesRef rb;
+    const GroupVTable *vt;
+    Context *ctx;
+    int rc = shplonk_check(E, handle, polys, d_polys, lens, k, points, npoints, &rb, &vt, &ctx);
+    if (rc) return rc;
+    if ((rc = check_device_vector(E, "d_out_w", d_out_w, ctx->device))) return rc;
+    return vt->shplonk_open_w(*ctx, polys, d_polys, lens, k, points, npoints, gamma, (hipStream_t)hip_stream, out_claimed, out_w, d_out_w,
+                              out_w_jac, rb.get());
+}
+
+GMSM_EXPORT int gmsm_shplonk_open_wprime(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                                         const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
+                                         const uint64_t *w, const void *d_w, const uint64_t *z, void *hip_stream, uint64_t *out_wprime_jac) {
+    const char *E = "gmsm_shplonk_open_wprime";
+    if (int rc0 = shplonk_nonempty(E, lens, k, points, npoints)) return rc0;
+    if (!claimed || !gamma || !z || !out_wprime_jac)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": claimed, gamma, z and out_wprime_jac must not be null");
+    if ((w == nullptr) == (d_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of w (host) / d_w (device)");
+    if ((polys && polys == out_wprime_jac) || (w && w == out_wprime_jac) || points == out_wprime_jac || claimed == out_wprime_jac)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": out_wprime_jac aliases an input (inputs are never modified)");
+    BasesRef rb;
+    const GroupVTable *vt;
+    Context *ctx;
+    int rc = shplonk_check(E, handle, polys, d_polys, lens, k, points, npoints, &rb, &vt, &ctx);
+    if (rc) return rc;
+    if ((rc = check_device_vector(E, "d_w", d_w, ctx->device))) return rc;
+    return vt->shplonk_open_wprime(*ctx, polys, d_polys, lens, k, points, npoints, claimed, gamma, w, d_w, z, (hipStream_t)hip_stream,
+                                   out_wprime_jac, rb.get());
+}
+
 // ------------------------------------------------------------------ ToLagrangeG1 (gmsm_group_fft.h)
 static const char *const ERR_POW2 = "len(coeffs) must be a power of 2";  // ToLagrangeG1, kzg/utils.go
 static const char *const ERR_G1_ONLY = "ToLagrangeG1 is defined for G1 only";

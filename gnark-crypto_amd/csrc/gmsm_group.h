@@ -20,6 +20,7 @@
 #include "gmsm_decompress.h"
 #include "gmsm_fft.h"
 #include "gmsm_poly.h"
+#include "gmsm_shplonk.h"
 #include "gmsm_group_fft.h"
 
 namespace gmsm {

@@ -302,6 +302,89 @@ struct VTableOf {
         memcpy(out_jac, &j, sizeof j);
         return GMSM_OK;
     }
+    // ---- shplonk.BatchOpen (gmsm_shplonk.h)
+    using SF = ShplonkField<typename G::FrP>;
+    static typename G::J commit_or_infinity(Context &ctx, Workspace &ws, const Fr *scalars, size_t n, const ResidentBases *resident, int *rc) {
+        typename G::J j{G::F::one(), G::F::one(), G::F::zero()};  // Commit of the zero polynomial
+        *rc = n ? G::multiexp_device(ctx, ws, nullptr, scalars, n, ws.stream, &j, resident) : GMSM_OK;
+        return j;
+    }
+    static int shplonk_open_w(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *points,
+                              const size_t *npoints, const uint64_t *gamma, hipStream_t caller, uint64_t *out_claimed, uint64_t *out_w,
+                              void *d_out_w, uint64_t *out_jac, const ResidentBases *resident) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        size_t total = 0, maxlen = 0, np = 0, wlen = 0;
+        for (size_t i = 0; i < k; ++i) {
+            total += lens[i], maxlen = std::max(maxlen, lens[i]), np += npoints[i];
+            if (lens[i] > npoints[i]) wlen = std::max(wlen, lens[i] - npoints[i]);  // the true length of w
+        }
+        const Fr *in;
+        int rc = poly_input(ws, polys, d_polys, total, caller, &in);
+        if (rc) return rc;
+        if (d_out_w && polys && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out_w
+        const size_t wbuf = out_w ? maxlen : 0;
+        if ((rc = ws.poly.ensure((np + wbuf + 2 * (maxlen - 1) + SF::chain_scratch(lens, npoints, k)) * sizeof(Fr)))) return rc;
+        Fr *rem = (Fr *)ws.poly.ptr, *w = out_w ? rem + np : (Fr *)d_out_w, *a = rem + np + wbuf, *b = a + (maxlen - 1), *scratch = b + (maxlen - 1);
+        Fr g;
+        memcpy(&g, gamma, sizeof g);
+        const Fr *pts = (const Fr *)points;
+        if ((rc = SF::chains(ws.stream, in, lens, k, pts, npoints, g, maxlen, rem, w, a, b, scratch))) return rc;
+        std::vector<Fr> d(np);
+        HIP_TRY(hipMemcpyAsync(d.data(), rem, np * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        if (out_w) HIP_TRY(hipMemcpyAsync(out_w, w, maxlen * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        // w is committed where it is: the resident MultiExp over its true length
+        const typename G::J j = commit_or_infinity(ctx, ws, w, wlen, resident, &rc);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        SF::claimed_from_remainders(pts, npoints, k, d.data(), (Fr *)out_claimed);
+        memcpy(out_jac, &j, sizeof j);
+        return GMSM_OK;
+    }
+    static int shplonk_open_wprime(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                                   const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
+                                   const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t caller, uint64_t *out_jac,
+                                   const ResidentBases *resident) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        size_t total = 0, maxlen = 0;
+        for (size_t i = 0; i < k; ++i) total += lens[i], maxlen = std::max(maxlen, lens[i]);
+        const Fr *in;
+        int rc = poly_input(ws, polys, d_polys, total, caller, &in);
+        if (rc) return rc;
+        if (d_w && polys && (rc = order_after(ws, caller))) return rc;  // d_w is the caller's stream's
+        // host part: c_i, Z_T(z), sum_i c_i r_i(z) and the (offset, length) pairs, in one staging vector of Fr-sized slots
+        const size_t ol_elems = (2 * k * 8 + sizeof(Fr) - 1) / sizeof(Fr), head = k + 2 + ol_elems;
+        std::vector<Fr> stage(head);
+        Fr g, zz;
+        memcpy(&g, gamma, sizeof g);
+        memcpy(&zz, z, sizeof zz);
+        SF::combine_coefficients((const Fr *)points, npoints, k, (const Fr *)claimed, g, zz, stage.data());
+        uint64_t *ol = (uint64_t *)(stage.data() + k + 2);
+        for (size_t i = 0, off = 0; i < k; off += lens[i], ++i) ol[2 * i] = off, ol[2 * i + 1] = lens[i];
+        const size_t wbuf = w ? maxlen : 0;
+        if ((rc = ws.poly.ensure((head + wbuf + maxlen + (maxlen - 1) + PF::scratch_elems(maxlen)) * sizeof(Fr)))) return rc;
+        Fr *coef = (Fr *)ws.poly.ptr, *wdev = coef + head, *l = wdev + wbuf, *h = l + maxlen, *scratch = h + (maxlen - 1);
+        HIP_TRY(hipMemcpyAsync(coef, stage.data(), head * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+        if (w) HIP_TRY(hipMemcpyAsync(wdev, w, maxlen * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+        const Fr *wsrc = w ? wdev : (const Fr *)d_w;
+        if ((rc = SF::combine(ws.stream, in, (const uint64_t *)(coef + k + 2), k, maxlen, coef, wsrc, l))) return rc;
+        // L(z) = 0 for true claimed values; the quotient does not depend on the remainder either way
+        if (maxlen > 1 && (rc = PF::suffix(ws.stream, PF::powers_of(z), l, maxlen, h, nullptr, scratch))) return rc;
+        const typename G::J j = commit_or_infinity(ctx, ws, h, maxlen - 1, resident, &rc);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));  // `stage` is pageable host memory: alive until here
+        memcpy(out_jac, &j, sizeof j);
+        return GMSM_OK;
+    }
+    static constexpr decltype(GroupVTable::shplonk_open_w) shplonk_w_entry() {
+        if constexpr (IS_G1) return &shplonk_open_w;
+        else return nullptr;
+    }
+    static constexpr decltype(GroupVTable::shplonk_open_wprime) shplonk_wprime_entry() {
+        if constexpr (IS_G1) return &shplonk_open_wprime;
+        else return nullptr;
+    }
     // ---- ToLagrangeG1 (gmsm_group_fft.h)
     static int to_lagrange(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
                            hipStream_t caller, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases) {
@@ -338,7 +421,8 @@ struct VTableOf {
                                        sizeof(typename G::Ext), &multiexp_host, &multiexp_device, &window_sums,
                                        &fold,           &jac_to_affine, &debug_decompose, &debug_field_op,
                                        &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info,
-                                       &poly_eval, &poly_div, &kzg_open, lagrange_entry(), (unsigned)G::FrP::MAX_ORDER};
+                                       &poly_eval, &poly_div, &kzg_open, lagrange_entry(), shplonk_w_entry(), shplonk_wprime_entry(),
+                                       (unsigned)G::FrP::MAX_ORDER};
         return &vt;
     }
 };

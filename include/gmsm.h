@@ -296,6 +296,35 @@ int gmsm_kzg_open(uint64_t handle, const uint64_t *poly, const void *d_poly, siz
 int gmsm_kzg_open_folded(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
                          const uint64_t *point, const uint64_t *gamma, void *hip_stream, uint64_t *out_h_jac);
 
+/* ---- shplonk.BatchOpen (ecc/<curve>/shplonk/shplonk.go:44-172) over registered G1 bases: polynomial i is opened on its own
+ *      set S_i of npoints[i] points. Two stateless entries, one per Fiat-Shamir challenge (deriveChallenge stays with the
+ *      caller, who bounces between them); results are bit-identical to the reference's. Polynomials as for the KZG
+ *      entries: k fr.Element vectors concatenated (lens[i] coefficients each), exactly one of a host pointer / a 16-byte
+ *      aligned device pointer produced on hip_stream, never modified. `points` holds sum_i npoints[i] fr.Element on the host,
+ *      polynomial i's set first to last in the order given; out_claimed / claimed use the same layout. Every call
+ *      returns when its results are complete; scratch comes from the workspace of the call.
+ *   gmsm_shplonk_open_w (given gamma): out_claimed = f_i(s) for s in S_i; w = (sum_i gamma^i Z_(T\S_i) (f_i - r_i)) / Z_T,
+ *      computed as sum_i gamma^i (f_i div Z_(S_i)) by a chain of npoints[i] divisions by (X - s) per polynomial, to exactly
+ *      one of out_w (host) / d_out_w (device): maxlen = max_i lens[i] elements, zero above the true degree;
+ *      out_w_jac = Commit(w) as Jacobian {X,Y,Z}.
+ *   gmsm_shplonk_open_wprime (given z): out_wprime_jac = Commit(L / (X - z)), L = sum_i gamma^i Z_(T\S_i)(z) (f_i - r_i(z))
+ *      - Z_T(z) w, with r_i interpolated from `claimed` and w (maxlen elements) from exactly one of w (host) / d_w (device,
+ *      e.g. what gmsm_shplonk_open_w wrote).
+ *   Both commitments go through the resident MultiExp (window tables included when the handle has them), over the true
+ *   lengths only; the zero polynomial commits to infinity.
+ *   Errors, all GMSM_ERR_ARG with a text: k == 0 or a null required pointer; both or none of a pair of pointers; an unknown
+ *   handle or a handle of G2 bases; an empty polynomial; npoints[i] == 0; two equal points inside one S_i - a departure:
+ *   the reference's interpolate inverts zero there and returns a meaningless proof without an error (equal points in
+ *   different sets are legal); and the reference's size condition, checked up front in both entries: it commits wPrime
+ *   over maxSizePolys + sum_i npoints[i] - 1 coefficients, maxSizePolys = max(max_i lens[i], max_i npoints[i] + 1)
+ *   (shplonk.go:66-83, :163-166) - more than the registered size is "invalid polynomial size (larger than SRS or == 0)". ---- */
+int gmsm_shplonk_open_w(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                        const uint64_t *points, const size_t *npoints, const uint64_t *gamma, void *hip_stream,
+                        uint64_t *out_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_w_jac);
+int gmsm_shplonk_open_wprime(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
+                             const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
+                             const uint64_t *w, const void *d_w, const uint64_t *z, void *hip_stream, uint64_t *out_wprime_jac);
+
 /* ---- ToLagrangeG1 (ecc/<curve>/kzg/utils.go:25-64): the Lagrange form of an SRS, out[i] = (1/n) sum_j w^(-ij) P_j with
  *      w = fr.Generator(n) - for P_j = [tau^j]G that is [L_i(tau)]G - as an inverse FFT over G1 points on the device
  *      (gmsm_group_fft.h). Results are canonical affine limbs (infinity = (0, 0)), bit-identical to the reference's.

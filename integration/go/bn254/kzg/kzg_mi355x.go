@@ -198,6 +198,11 @@ func ReadFromResident(r io.Reader, windowTables bool, subgroupCheck bool) (*Resi
 // Size is the number of registered points.
 func (rk *ResidentProvingKey) Size() int { return rk.n }
 
+// Resident returns the handle of the registered bases (0 in builds without the mi355x tag) and the host copy of the key
+// (empty after ReadDumpResident / ReadFromResident): what packages built on kzg, such as shplonk, need to call the C ABI
+// over this key.
+func (rk *ResidentProvingKey) Resident() (uint64, ProvingKey) { return uint64(rk.handle), rk.host }
+
 // Commit commits to a polynomial over the resident SRS: Commit(p, pk) of kzg.go:159-176 without the copy of pk.
 func (rk *ResidentProvingKey) Commit(p []fr.Element, nbTasks ...int) (Digest, error) {
 	if len(p) == 0 || len(p) > rk.n {

@@ -57,6 +57,10 @@ func ReadFromResident(r io.Reader, windowTables bool, subgroupCheck bool) (*Resi
 // Size is the number of points of the key.
 func (rk *ResidentProvingKey) Size() int { return len(rk.host.G1) }
 
+// Resident returns 0 (no device handle in this build) and the key itself: what packages built on kzg, such as shplonk,
+// need to run the reference's functions over this key.
+func (rk *ResidentProvingKey) Resident() (uint64, ProvingKey) { return 0, rk.host }
+
 // Commit is Commit(p, pk) (kzg.go:159-176).
 func (rk *ResidentProvingKey) Commit(p []fr.Element, nbTasks ...int) (Digest, error) {
 	return Commit(p, rk.host, nbTasks...)
