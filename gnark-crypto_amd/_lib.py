@@ -231,7 +231,8 @@ def last_error():
 
 
 # enum gmsm_option (include/gmsm.h)
-OPTIONS = {"window_bits": 0, "tables": 1, "max_run": 2, "host_ranges": 3, "fixed_base_bits": 4, "spin_wait_us": 5, "small_bits": 6, "small_max": 7, "split": 8, "glv": 9, "small_quad": 10}
+OPTIONS = {"window_bits": 0, "tables": 1, "max_run": 2, "host_ranges": 3, "fixed_base_bits": 4, "spin_wait_us": 5, "small_bits": 6, "small_max": 7, "split": 8, "glv": 9, "small_quad": 10,
+           "poly_lane_bits": 11}
 
 
 def set_option(name, value):

@@ -69,6 +69,7 @@ struct Options {
     std::atomic<unsigned> small_max{0};        // GMSM_OPT_SMALL_MAX: largest call the fused kernel takes (0 = the measured default)
     std::atomic<unsigned> glv{1};              // GMSM_OPT_GLV: half scalars (gmsm_glv.h): 0 never, 1 the fused small-n kernel, 2 the sorted pipeline too
     std::atomic<unsigned> small_quad{0};       // GMSM_OPT_SMALL_QUAD: bucket phase of the fused kernel on lane quads: 0 by size, 1 never (narrow types), 2 always
+    std::atomic<unsigned> poly_lane_bits{0};   // GMSM_OPT_POLY_LANE_BITS (tests): 0 = lane width of the suffix scan by length, k in 1..6 = 2^(k-1) coefficients
 };
 Options &options();
 

@@ -1815,6 +1815,10 @@ GMSM_EXPORT int gmsm_set_option(int key, unsigned value) {
             if (value > 2) return fail(GMSM_ERR_ARG, "GMSM_OPT_SMALL_QUAD: 0 by call size, 1 never, 2 always");
             o.small_quad.store(value);
             return GMSM_OK;
+        case GMSM_OPT_POLY_LANE_BITS:
+            if (value > 6) return fail(GMSM_ERR_ARG, "GMSM_OPT_POLY_LANE_BITS: 0 (lane width by length) or 1..6 (lanes of 2^(k-1) coefficients)");
+            o.poly_lane_bits.store(value);
+            return GMSM_OK;
         case GMSM_OPT_SPIN_WAIT_US:
             if (value > 1000000) return fail(GMSM_ERR_ARG, "GMSM_OPT_SPIN_WAIT_US: at most 1000000");
             o.spin_wait_us.store(value);
@@ -1837,6 +1841,7 @@ GMSM_EXPORT unsigned gmsm_get_option(int key) {
         case GMSM_OPT_SPLIT: return o.split.load();
         case GMSM_OPT_GLV: return o.glv.load();
         case GMSM_OPT_SMALL_QUAD: return o.small_quad.load();
+        case GMSM_OPT_POLY_LANE_BITS: return o.poly_lane_bits.load();
         default: return 0;
     }
 }

@@ -232,9 +232,9 @@ struct VTableOf {
         *out = (const Fr *)d_polys;
         return GMSM_OK;
     }
-    static size_t poly_scratch(const size_t *lens, size_t k) {
+    static size_t poly_scratch(const size_t *lens, size_t k, unsigned lanes) {
         size_t s = 0;
-        for (size_t i = 0; i < k; ++i) s = std::max(s, PF::scratch_elems(lens[i]));
+        for (size_t i = 0; i < k; ++i) s = std::max(s, PF::scratch_elems(lens[i], lanes));
         return s;
     }
     static int poly_eval(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
@@ -246,11 +246,12 @@ struct VTableOf {
         const Fr *in;
         int rc = poly_input(ws, polys, d_polys, total, caller, &in);
         if (rc) return rc;
-        if ((rc = ws.poly.ensure((k + poly_scratch(lens, k)) * sizeof(Fr)))) return rc;
+        const unsigned lanes = PF::lane_option();
+        if ((rc = ws.poly.ensure((k + poly_scratch(lens, k, lanes)) * sizeof(Fr)))) return rc;
         Fr *vals = (Fr *)ws.poly.ptr, *scratch = vals + k;
         const FftPowers<typename G::FrP> pw = PF::powers_of(point);
         for (size_t i = 0, off = 0; i < k; off += lens[i], ++i)
-            if ((rc = PF::suffix(ws.stream, pw, in + off, lens[i], nullptr, vals + i, scratch))) return rc;
+            if ((rc = PF::suffix(ws.stream, pw, in + off, lens[i], nullptr, vals + i, scratch, lanes))) return rc;
         HIP_TRY(hipMemcpyAsync(out_values, vals, k * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
         HIP_TRY(hipStreamSynchronize(ws.stream));
         return GMSM_OK;
@@ -264,9 +265,10 @@ struct VTableOf {
         if (rc) return rc;
         if (d_out_h && poly && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out_h
         const size_t hbuf = out_h ? n - 1 : 0;
-        if ((rc = ws.poly.ensure((1 + hbuf + PF::scratch_elems(n)) * sizeof(Fr)))) return rc;
+        const unsigned lanes = PF::lane_option();
+        if ((rc = ws.poly.ensure((1 + hbuf + PF::scratch_elems(n, lanes)) * sizeof(Fr)))) return rc;
         Fr *value = (Fr *)ws.poly.ptr, *h = out_h ? value + 1 : (Fr *)d_out_h, *scratch = value + 1 + hbuf;
-        if ((rc = PF::suffix(ws.stream, PF::powers_of(point), in, n, n > 1 ? h : nullptr, value, scratch))) return rc;
+        if ((rc = PF::suffix(ws.stream, PF::powers_of(point), in, n, n > 1 ? h : nullptr, value, scratch, lanes))) return rc;
         if (out_h && n > 1) HIP_TRY(hipMemcpyAsync(out_h, h, (n - 1) * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
         if (out_value) HIP_TRY(hipMemcpyAsync(out_value, value, sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
         HIP_TRY(hipStreamSynchronize(ws.stream));
@@ -283,7 +285,8 @@ struct VTableOf {
         if (rc) return rc;
         const bool folds = k > 1;
         const size_t ol_elems = folds ? (2 * k * 8 + sizeof(Fr) - 1) / sizeof(Fr) : 0;
-        const size_t elems = 1 + (maxlen - 1) + (folds ? maxlen : 0) + ol_elems + PF::scratch_elems(maxlen);
+        const unsigned lanes = PF::lane_option();
+        const size_t elems = 1 + (maxlen - 1) + (folds ? maxlen : 0) + ol_elems + PF::scratch_elems(maxlen, lanes);
         if ((rc = ws.poly.ensure(elems * sizeof(Fr)))) return rc;
         Fr *value = (Fr *)ws.poly.ptr, *h = value + 1, *folded = h + (maxlen - 1);
         uint64_t *off_len = (uint64_t *)(folded + (folds ? maxlen : 0));
@@ -293,7 +296,7 @@ struct VTableOf {
             if ((rc = PF::fold(ws.stream, in, lens, k, maxlen, gamma, off_len, folded))) return rc;
             v = folded;
         }
-        if ((rc = PF::suffix(ws.stream, PF::powers_of(point), v, maxlen, h, value, scratch))) return rc;
+        if ((rc = PF::suffix(ws.stream, PF::powers_of(point), v, maxlen, h, value, scratch, lanes))) return rc;
         if (out_claimed) HIP_TRY(hipMemcpyAsync(out_claimed, value, sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
         // the quotient is committed where it is: the resident MultiExp over the first maxlen - 1 bases
         typename G::J j;
@@ -324,12 +327,13 @@ struct VTableOf {
         if (rc) return rc;
         if (d_out_w && polys && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out_w
         const size_t wbuf = out_w ? maxlen : 0;
-        if ((rc = ws.poly.ensure((np + wbuf + 2 * (maxlen - 1) + SF::chain_scratch(lens, npoints, k)) * sizeof(Fr)))) return rc;
+        const unsigned lanes = PF::lane_option();
+        if ((rc = ws.poly.ensure((np + wbuf + 2 * (maxlen - 1) + SF::chain_scratch(lens, npoints, k, lanes)) * sizeof(Fr)))) return rc;
         Fr *rem = (Fr *)ws.poly.ptr, *w = out_w ? rem + np : (Fr *)d_out_w, *a = rem + np + wbuf, *b = a + (maxlen - 1), *scratch = b + (maxlen - 1);
         Fr g;
         memcpy(&g, gamma, sizeof g);
         const Fr *pts = (const Fr *)points;
-        if ((rc = SF::chains(ws.stream, in, lens, k, pts, npoints, g, maxlen, rem, w, a, b, scratch))) return rc;
+        if ((rc = SF::chains(ws.stream, in, lens, k, pts, npoints, g, maxlen, rem, w, a, b, scratch, lanes))) return rc;
         std::vector<Fr> d(np);
         HIP_TRY(hipMemcpyAsync(d.data(), rem, np * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
         if (out_w) HIP_TRY(hipMemcpyAsync(out_w, w, maxlen * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
@@ -363,14 +367,15 @@ struct VTableOf {
         uint64_t *ol = (uint64_t *)(stage.data() + k + 2);
         for (size_t i = 0, off = 0; i < k; off += lens[i], ++i) ol[2 * i] = off, ol[2 * i + 1] = lens[i];
         const size_t wbuf = w ? maxlen : 0;
-        if ((rc = ws.poly.ensure((head + wbuf + maxlen + (maxlen - 1) + PF::scratch_elems(maxlen)) * sizeof(Fr)))) return rc;
+        const unsigned lanes = PF::lane_option();
+        if ((rc = ws.poly.ensure((head + wbuf + maxlen + (maxlen - 1) + PF::scratch_elems(maxlen, lanes)) * sizeof(Fr)))) return rc;
         Fr *coef = (Fr *)ws.poly.ptr, *wdev = coef + head, *l = wdev + wbuf, *h = l + maxlen, *scratch = h + (maxlen - 1);
         HIP_TRY(hipMemcpyAsync(coef, stage.data(), head * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
         if (w) HIP_TRY(hipMemcpyAsync(wdev, w, maxlen * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
         const Fr *wsrc = w ? wdev : (const Fr *)d_w;
         if ((rc = SF::combine(ws.stream, in, (const uint64_t *)(coef + k + 2), k, maxlen, coef, wsrc, l))) return rc;
         // L(z) = 0 for true claimed values; the quotient does not depend on the remainder either way
-        if (maxlen > 1 && (rc = PF::suffix(ws.stream, PF::powers_of(z), l, maxlen, h, nullptr, scratch))) return rc;
+        if (maxlen > 1 && (rc = PF::suffix(ws.stream, PF::powers_of(z), l, maxlen, h, nullptr, scratch, lanes))) return rc;
         const typename G::J j = commit_or_infinity(ctx, ws, h, maxlen - 1, resident, &rc);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(ws.stream));  // `stage` is pageable host memory: alive until here

@@ -130,19 +130,28 @@ struct PolyField {
 
     // lane width 2^tb by length: long vectors take long lanes (the scan's ~7 products per lane are spread over more
     // coefficients), short ones short lanes (more lanes in flight)
-    static unsigned lane_bits(size_t m) { return m > ((size_t)1 << 18) ? 5u : m > ((size_t)1 << 14) ? 4u : 3u; }
+    // GMSM_OPT_POLY_LANE_BITS (lanes = k in 1..6) forces 2^(k-1) for every length: the tests reach the carry pass's lanes of
+    // several tiles, and every lane width on ragged tiles, at lengths a big-int model handles
+    static unsigned lane_bits(size_t m, unsigned lanes) {
+        if (lanes) return lanes - 1;
+        return m > ((size_t)1 << 18) ? 5u : m > ((size_t)1 << 14) ? 4u : 3u;
+    }
+    // The switch, read ONCE per ABI call: the caller hands the same value to scratch_elems and to suffix, so the scratch a call
+    // sized and the launches it makes agree even when another thread sets the switch meanwhile.
+    static unsigned lane_option() { return options().poly_lane_bits.load(std::memory_order_relaxed); }
 
     // scratch elements suffix() needs for a vector of m coefficients
-    static size_t scratch_elems(size_t m) {
-        const unsigned tb = lane_bits(m);
+    static size_t scratch_elems(size_t m, unsigned lanes) {
+        const unsigned tb = lane_bits(m, lanes);
         const size_t L = (size_t)POLY_TPB << tb, nt = (m + L - 1) / L;
         return nt <= 1 ? 0 : nt * POLY_TPB + 2 * nt + POLY_TPB;
     }
 
     // The suffix recurrence over v (m >= 1 coefficients, device) at the point whose powers are pw, on `stream`:
-    // h (m - 1 elements, may be null) and y_0 = f(a) (*value, device, may be null). scratch: scratch_elems(m) elements.
-    static int suffix(hipStream_t stream, const FftPowers<FrP> &pw, const Fr *v, size_t m, Fr *h, Fr *value, Fr *scratch) {
-        const unsigned tb = lane_bits(m), logL = POLY_LOG_TPB + tb;
+    // h (m - 1 elements, may be null) and y_0 = f(a) (*value, device, may be null). scratch: scratch_elems(m, lanes) elements,
+    // lanes: the call's lane_option().
+    static int suffix(hipStream_t stream, const FftPowers<FrP> &pw, const Fr *v, size_t m, Fr *h, Fr *value, Fr *scratch, unsigned lanes) {
+        const unsigned tb = lane_bits(m, lanes), logL = POLY_LOG_TPB + tb;
         const size_t L = (size_t)1 << logL, nt = (m + L - 1) / L;
         if (nt <= 1) {
             hipLaunchKernelGGL((k_poly_lanes<FrP, 1>), dim3(1), dim3(POLY_TPB), 0, stream, v, m, pw, 0u, tb, nullptr, nullptr, h, 1u, value);

@@ -63,17 +63,18 @@ struct ShplonkField {
     }
 
     // scratch PolyField::suffix needs along the chain of polynomial lengths len, len - 1, ... (lane widths change with the length)
-    static size_t chain_scratch(const size_t *lens, const size_t *npoints, size_t k) {
+    static size_t chain_scratch(const size_t *lens, const size_t *npoints, size_t k, unsigned lanes) {
         size_t s = 0;
         for (size_t i = 0; i < k; ++i)
-            for (size_t j = 0; j < npoints[i] && j < lens[i]; ++j) s = std::max(s, PF::scratch_elems(lens[i] - j));
+            for (size_t j = 0; j < npoints[i] && j < lens[i]; ++j) s = std::max(s, PF::scratch_elems(lens[i] - j, lanes));
         return s;
     }
 
     // The chains and the accumulation on `stream`: rem (sum_i m_i elements, device) receives d_(i,j), w (maxlen elements,
-    // device) sum_i gamma^i q_i. a, b: ping-pong vectors of maxlen - 1 elements; scratch: chain_scratch elements.
+    // device) sum_i gamma^i q_i. a, b: ping-pong vectors of maxlen - 1 elements; scratch: chain_scratch elements for the same
+    // lanes (the call's PolyField::lane_option()).
     static int chains(hipStream_t stream, const Fr *polys, const size_t *lens, size_t k, const Fr *points, const size_t *npoints,
-                      const Fr &gamma, size_t maxlen, Fr *rem, Fr *w, Fr *a, Fr *b, Fr *scratch) {
+                      const Fr &gamma, size_t maxlen, Fr *rem, Fr *w, Fr *a, Fr *b, Fr *scratch, unsigned lanes) {
         size_t total_points = 0;
         for (size_t i = 0; i < k; ++i) total_points += npoints[i];
         HIP_TRY(hipMemsetAsync(rem, 0, total_points * sizeof(Fr), stream));  // a chain that runs out of coefficients leaves d = 0
@@ -85,7 +86,7 @@ struct ShplonkField {
             size_t n = lens[i];
             for (size_t j = 0; j < npoints[i] && n > 0; ++j, --n) {
                 Fr *dst = (j & 1) ? b : a;
-                if ((rc = PF::suffix(stream, FftField<FrP>::powers_of(points[p + j]), cur, n, n > 1 ? dst : nullptr, rem + p + j, scratch)))
+                if ((rc = PF::suffix(stream, FftField<FrP>::powers_of(points[p + j]), cur, n, n > 1 ? dst : nullptr, rem + p + j, scratch, lanes)))
                     return rc;
                 cur = dst;
             }

@@ -412,7 +412,8 @@ int gmsm_get_stage_launches(unsigned long *out_launches, int max_stages);
 
 /* ---- switches (process-wide).  GMSM_OPT_WINDOW_BITS and GMSM_OPT_TABLES take their initial value from the environment
  *      variables GMSM_C / GMSM_TABLES once, when the library is first used; nothing reads the environment per call.
- *      GMSM_OPT_MAX_RUN / GMSM_OPT_HOST_RANGES exist for the tests of the point-range splits (0 = off). ---- */
+ *      GMSM_OPT_MAX_RUN / GMSM_OPT_HOST_RANGES exist for the tests of the point-range splits (0 = off),
+ *      GMSM_OPT_POLY_LANE_BITS for the tests of the polynomial scan's launch shapes (0 = off). ---- */
 enum gmsm_option {
     GMSM_OPT_WINDOW_BITS = 0, /* 0 = the library's measured table per group and size, 2..20 = forced (cost only: the
                                  affine result does not depend on c, multiexp_test.go:95-126) */
@@ -440,8 +441,13 @@ enum gmsm_option {
                                  k1 P + k2 phi(P) instead of s P. The reference's MultiExp never uses the endomorphism and is
                                  the integer combination on ANY curve point: GMSM_OPT_GLV = 0 is exactly that
                                  (tests/test_gpu_glv.py::test_glv_off_is_the_integer_combination_outside_the_subgroup) */
-    GMSM_OPT_SMALL_QUAD = 10  /* bucket phase of the fused small-n kernel on lane quads: 0 (default) by call size, 1 never,
+    GMSM_OPT_SMALL_QUAD = 10, /* bucket phase of the fused small-n kernel on lane quads: 0 (default) by call size, 1 never,
                                  2 always (the Fp2 groups and BW6-761 always run it on quads) */
+    GMSM_OPT_POLY_LANE_BITS = 11 /* for the tests of the suffix scan behind gmsm_poly_eval, gmsm_poly_div_x_minus_a, the gmsm_kzg_open
+                                 and the gmsm_shplonk_open entries: 0 (default) = lanes of 8, 16 or 32 coefficients by length; k in 1..6 =
+                                 lanes of 2^(k-1) coefficients whatever the length (a tile is 256 lanes, so k = 1 reaches the
+                                 carry pass's lanes of several tiles at 2^16 coefficients instead of 2^21). Cost only: every
+                                 output is the same field element. Read once per call. */
 };
 int gmsm_set_option(int key, unsigned value);
 unsigned gmsm_get_option(int key);

@@ -200,6 +200,29 @@ def test_options_and_lifecycle_entries_need_no_device(gm):
     assert len(gm.get_devices()) == 1
 
 
+def test_option_names_mirror_the_header_enum(gm):
+    """gnark-crypto_amd/_lib.py OPTIONS is enum gmsm_option of include/gmsm.h, name for name and value for value."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gmsm.h")).read(), flags=re.S)
+    body = re.search(r"enum gmsm_option \{(.*?)\};", hdr, flags=re.S).group(1)
+    enum = {name.lower(): int(v) for name, v in re.findall(r"GMSM_OPT_([A-Z_]+)\s*=\s*(\d+)", body)}
+    assert enum == gm._lib.OPTIONS and enum["poly_lane_bits"] == 11
+
+
+def test_poly_lane_bits_option_needs_no_device(gm):
+    """GMSM_OPT_POLY_LANE_BITS: 0 (the default, lane width by length) or 1..6, anything else the argument error with the range"""
+    assert gm.get_option("poly_lane_bits") == 0
+    for k in range(0, 7):
+        with gm.options(poly_lane_bits=k):
+            assert gm.get_option("poly_lane_bits") == k
+        assert gm.get_option("poly_lane_bits") == 0
+    lib = gm._lib.load()
+    for bad in (7, 8, 32, 2**32 - 1):
+        with pytest.raises(ValueError, match=r"GMSM_OPT_POLY_LANE_BITS: 0 .* or 1\.\.6"):
+            gm.set_option("poly_lane_bits", bad)
+        assert lib.gmsm_set_option(gm._lib.OPTIONS["poly_lane_bits"], bad) == gm._lib.GMSM_ERR_ARG
+        assert gm.get_option("poly_lane_bits") == 0
+
+
 def test_race_client_builds_as_c(tmp_path):
     """tests/c/race_client.c (the sanitizer workload) is plain C99 + pthreads against include/gmsm.h and links to the shipped
     library; without a device it says so and exits 77."""

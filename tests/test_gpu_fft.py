@@ -1,6 +1,7 @@
 """fr/fft on the device (gmsm_fft_*, gnark-crypto_amd/fft.py) against the oracle, bit for bit: every decimation,
 direction and coset combination, sizes 1 .. 2^16 for the three scalar fields, 2^22 for BN254, plus the reference's
-round-trip properties (ecc/bn254/fr/fft/fft_test.go) at a size the oracle does not need to touch."""
+round-trip properties (ecc/bn254/fr/fft/fft_test.go) at a size the oracle does not need to touch; then the pass shapes the
+size table of FftField::run selects between and above those sizes (2^15, 2^17 .. 2^19, 2^21, 2^22 for the other fields)."""
 import numpy as np
 import pytest
 
@@ -168,4 +169,119 @@ def test_fft_2_pow_22_device_resident(gm, oracle_mod):
     gm.fft.BitReverse(curve, d_a=t.data_ptr(), n=n, stream=stream)
     gm.fft.BitReverse(curve, d_a=t.data_ptr(), n=n, stream=stream)
     assert (t.cpu().numpy().view(np.uint64) == a).all()
+    d.release()
+
+
+# ---- pass shapes of FftField::run (gmsm_fft.h) that the sizes above do not select. The low pass takes LOWB bits (10 for the
+# 32-byte fields, 9 for BW6-761), the rest goes in passes of at most 8 bits (tiles of 2^B rows x 8 elements), split unequally
+# when it does not divide; 512 threads per tile from 2^22 on.
+def _pass_bits(curve, logn):
+    """(low pass bits, [high pass bits]) as FftField::run cuts them"""
+    low = min(logn, 9 if curve == "bw6_761" else 10)
+    rest, out = logn - low, []
+    nhi = (rest + 7) // 8
+    for k in range(nhi):
+        b = -(-rest // (nhi - k))
+        out.append(b)
+        rest -= b
+    return low, out
+
+
+def test_pass_shapes_named_below():
+    assert [_pass_bits("bn254", lg)[1] for lg in (15, 17, 18, 19, 21)] == [[5], [7], [8], [5, 4], [6, 5]]
+    assert [_pass_bits("bw6_761", lg)[1] for lg in (15, 17, 18, 19, 22)] == [[6], [8], [5, 4], [5, 5], [7, 6]]
+    assert _pass_bits("bls12_381", 22)[1] == [6, 6]
+
+
+@pytest.mark.parametrize("curve", CURVE_NAMES)
+@pytest.mark.parametrize("logn", [15, 17, 18, 19])
+def test_fft_matches_oracle_high_pass_shapes(gm, oracle_mod, curve, logn):
+    """Single high passes of 5, 7 and 8 bits and the 5+4 split (32-byte fields), 6 and 8 bits, 5+4 and 5+5 (BW6-761); the
+    8-bit pass's tile of 2^11 lazy elements is the largest dynamic-LDS request the library makes."""
+    F = oracle_mod.FFT(curve)
+    c = F.curve
+    n = 1 << logn
+    a = random_field_limbs(rng_for(85, logn, c.fr_limbs), c.r, c.fr_limbs, n)
+    d = gm.fft.NewDomain(curve, n)
+    for inverse in (False, True):
+        for dec in (gm.fft.DIT, gm.fft.DIF):
+            for coset in (False, True):
+                opts = (gm.fft.OnCoset(),) if coset else ()
+                got = (d.FFTInverse if inverse else d.FFT)(a, dec, *opts)
+                want = F.transform(a, inverse=inverse, decimation=dec, coset=coset)
+                assert (got == want).all(), (inverse, dec, coset)
+    d.release()
+
+
+def _device_resident(gm, oracle_mod, curve, logn, seed, oracle_coset_and_inverse):
+    """The form of test_fft_2_pow_22_device_resident: forward DIF against the oracle, DIF -> inverse DIT restores the input, the
+    coset pair does the same, BitReverse twice; with oracle_coset_and_inverse the coset forward and both inverse-DIT
+    transforms are compared with the oracle as well."""
+    import torch
+    F = oracle_mod.FFT(curve)
+    c = F.curve
+    n = 1 << logn
+    a = random_field_limbs(rng_for(seed, logn, c.fr_limbs), c.r, c.fr_limbs, n)
+    d = gm.fft.NewDomain(curve, n)
+    t = torch.from_numpy(a.view(np.int64)).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+    host = lambda: t.cpu().numpy().view(np.uint64)
+    d.fft_device(t.data_ptr(), gm.fft.DIF, stream=stream)
+    fwd = host()
+    assert (fwd == F.transform(a, decimation=oracle_mod.DIF)).all()
+    d.fft_device(t.data_ptr(), gm.fft.DIT, inverse=True, stream=stream)
+    assert (host() == a).all()
+    d.fft_device(t.data_ptr(), gm.fft.DIF, gm.fft.OnCoset(), stream=stream)
+    if oracle_coset_and_inverse:
+        assert (host() == F.transform(a, decimation=oracle_mod.DIF, coset=True)).all()
+    d.fft_device(t.data_ptr(), gm.fft.DIT, gm.fft.OnCoset(), inverse=True, stream=stream)
+    assert (host() == a).all()
+    if oracle_coset_and_inverse:  # the inverse DIT of a vector that is not a transform of anything: the input itself
+        for coset in (False, True):
+            opts = (gm.fft.OnCoset(),) if coset else ()
+            assert (d.FFTInverse(a, gm.fft.DIT, *opts) == F.transform(a, inverse=True, decimation=oracle_mod.DIT, coset=coset)).all(), coset
+    gm.fft.BitReverse(curve, d_a=t.data_ptr(), n=n, stream=stream)
+    gm.fft.BitReverse(curve, d_a=t.data_ptr(), n=n, stream=stream)
+    assert (host() == a).all()
+    d.release()
+
+
+@pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
+def test_fft_2_pow_21_unequal_split(gm, oracle_mod, curve):
+    """2^21 for the 32-byte fields: 10 + 6 + 5. Forward DIF and inverse DIT, plain and on the coset, against the oracle; the
+    round trips on the device buffer."""
+    _device_resident(gm, oracle_mod, curve, 21, 86, True)
+
+
+@pytest.mark.parametrize("curve", ["bls12_381", "bw6_761"])
+def test_fft_2_pow_22_device_resident_other_fields(gm, oracle_mod, curve):
+    """The 512-thread passes for the fields test_fft_2_pow_22_device_resident leaves out (BW6-761: a low tile of 256
+    butterflies per stage under 512 threads, and the 7 + 6 split)."""
+    _device_resident(gm, oracle_mod, curve, 22, 87, False)
+
+
+@pytest.mark.parametrize("curve", CURVE_NAMES)
+def test_fft_class_edges_2_pow_18(gm, oracle_mod, curve):
+    """The inputs of test_fft_class_edges at 2^18: an 8-bit high pass for the 32-byte fields (the most stages between two
+    reductions of a high pass), the 5+4 split for BW6-761."""
+    F = oracle_mod.FFT(curve)
+    c = F.curve
+    n = 1 << 18
+    rm1 = np.array([(c.r - 1 >> (64 * k)) & (2**64 - 1) for k in range(c.fr_limbs)], dtype=np.uint64)
+    fr = oracle_mod.Field(f"{c.name}_fr", c.fr_limbs)
+    top = np.tile(fr.to_mont(rm1), (n, 1))  # Montgomery form of r - 1
+    raw = np.tile(rm1, (n, 1))              # the limbs r - 1 themselves: the largest canonical limb pattern
+    alt = raw.copy()
+    alt[1::2] = 0
+    spike = np.zeros_like(raw)
+    spike[n // 3] = rm1
+    d = gm.fft.NewDomain(curve, n)
+    for a in (top, raw, alt, spike, np.zeros_like(raw)):
+        for inverse in (False, True):
+            for dec in (gm.fft.DIT, gm.fft.DIF):
+                for coset in (False, True):
+                    opts = (gm.fft.OnCoset(),) if coset else ()
+                    got = (d.FFTInverse if inverse else d.FFT)(a, dec, *opts)
+                    want = F.transform(a, inverse=inverse, decimation=dec, coset=coset)
+                    assert (got == want).all(), (inverse, dec, coset)
     d.release()

@@ -115,3 +115,36 @@ def test_glv_off_is_the_integer_combination_outside_the_subgroup(gm, oracle_mod,
             assert err is None and (aff == expected).all()
     aff, err = g.MultiExp(pts, sc)                           # default (GLV on): defined, but a different combination
     assert err is None
+
+
+@pytest.mark.parametrize("curve,which", ALL_GROUPS)
+def test_glv_every_built_width_and_every_default_plan(gm, oracle_mod, curve, which):
+    """k_decompose_glv is instantiated per window width, each with its own top-window geometry (top bits, the no-borrow top
+    digit, uint16 or uint32 digit arrays): the widths test_glv_pipeline_matches_oracle does not force - 12, 14, 15, 18, 20,
+    of which 14 and 15 are what BW6-761 at 2^18 and BLS12-381 G2 at 2^19 run by default - and then whatever (width, entries
+    per point) gmsm_default_plan selects between 2^11 and 2^21, so a new row of the table brings its own case. (The widths
+    the fused small-n kernel reports for the smallest sizes go through the sorted pipeline here like the others; below the
+    built GLV widths that is the plain decomposition at that width.)"""
+    import torch
+    g = (gm.G1Affine if which == "g1" else gm.G2Affine)(curve)
+    gj = (gm.G1Jac if which == "g1" else gm.G2Jac)(curve)
+    o = oracle_mod.Oracle(curve, which)
+    n = 20011
+    pts, sc = _inputs(o, g, n, 0)
+    expected = o.msm_affine(pts, sc, nthreads=8)
+    d_pts = torch.from_numpy(pts.view(np.int64)).cuda()
+    d_sc = torch.from_numpy(sc.view(np.int64)).cuda()
+    device = lambda: gj.jac_to_affine(gj.multiexp_device(d_pts.data_ptr(), d_sc.data_ptr(), n))
+    plans = {(p["window_bits"], p["entries_per_point"]) for p in (gj.default_plan(1 << lg) for lg in range(11, 22))}
+    assert all(e in (1, 2) for _, e in plans)
+    covered = set()
+    for c in (12, 14, 15, 18, 20):
+        with gm.options(glv=2, small_bits=1, window_bits=c):
+            assert (device() == expected).all(), c
+            if c in (14, 15):
+                aff, err = g.MultiExp(pts, sc)
+                assert err is None and (aff == expected).all(), c
+        covered.add((c, 2))
+    for c, entries in sorted(plans - covered):
+        with gm.options(glv=2 if entries == 2 else 0, small_bits=1, window_bits=c):
+            assert (device() == expected).all(), (c, entries)
