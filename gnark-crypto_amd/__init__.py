@@ -9,3 +9,4 @@ from ._lib import options, set_option, get_option, trim, shutdown  # noqa: F401 
 from . import fft  # noqa: F401  (fr/fft mirror: fft.NewDomain, fft.DIT / fft.DIF, fft.OnCoset, fft.BitReverse)
 from . import kzg  # noqa: F401  (kzg mirror: kzg.Open, kzg.BatchOpenSinglePoint, kzg.PolyEval, kzg.DividePolyByXMinusA, kzg.ToLagrangeG1)
 from . import shplonk  # noqa: F401  (shplonk mirror: shplonk.BatchOpen, shplonk.OpenW, shplonk.OpenWPrime)
+from . import fflonk  # noqa: F401  (fflonk mirror: fflonk.Fold, fflonk.FoldAndCommit, fflonk.BatchOpen, fflonk.OpenW, fflonk.OpenWPrime)

@@ -716,6 +716,24 @@ struct GroupVTable {
                                const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
                                const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t stream, uint64_t *out_jac,
                                const ResidentBases *resident);
+    // fflonk (gmsm_fflonk.h). Packs: all polynomials of all k packs concatenated, lens[] per polynomial, pack_sizes[] per pack.
+    //   fflonk_next_divisor: getNextDivisorRMinusOne over the group's scalar field, host only; false when there is none
+    //   fflonk_check: every refusal that depends on the packs and the points (points == null: the packs alone), host only;
+    //                 `registered` bases for the size condition of the two open entries (check_size)
+    //   fflonk_fold: Fold of one pack to out (host) / d_out (device) / the workspace (both null), and with `resident` its Commit
+    //   fflonk_open_w / fflonk_open_wprime: the two halves of fflonk.BatchOpen; nullptr for the G2 groups
+    bool (*fflonk_next_divisor)(size_t n, size_t *t);
+    int (*fflonk_check)(const char *entry, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
+                        const size_t *npoints, bool check_size, size_t registered);
+    int (*fflonk_fold)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys, hipStream_t stream,
+                       uint64_t *out, void *d_out, const ResidentBases *resident, uint64_t *out_jac);
+    int (*fflonk_open_w)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes, size_t k,
+                         const uint64_t *points, const size_t *npoints, const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed,
+                         uint64_t *out_folded_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_jac, const ResidentBases *resident);
+    int (*fflonk_open_wprime)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
+                              size_t k, const uint64_t *points, const size_t *npoints, const uint64_t *folded_claimed,
+                              const uint64_t *gamma, const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t stream,
+                              uint64_t *out_jac, const ResidentBases *resident);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

@@ -1503,6 +1503,141 @@ GMSM_EXPORT int gmsm_shplonk_open_wprime(uint64_t handle, const uint64_t *polys,
                                    out_wprime_jac, rb.get());
 }
 
+// ------------------------------------------------------------------ fflonk Fold, FoldAndCommit, BatchOpen (gmsm_fflonk.h)
+static const char *const ERR_FFLONK_G1 = "fflonk commits and opens over G1 bases only";
+
+GMSM_EXPORT int gmsm_fflonk_next_divisor(int group, size_t n, size_t *out_t) {
+    VT_OR_FAIL(group);
+    const char *E = "gmsm_fflonk_next_divisor";
+    if (!out_t) return fail(GMSM_ERR_ARG, std::string(E) + ": out_t is null");
+    if (n == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": n == 0");
+    if (!vt->fflonk_next_divisor(n, out_t))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": did not find any divisor of r-1 within 100 trials above " + std::to_string(n));
+    return GMSM_OK;
+}
+
+// One pack for Fold / FoldAndCommit: the pointer checks, then the pack's own (host only)
+static int fflonk_pack_args(const char *E, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys) {
+    if (npolys == 0 || !lens) return fail(GMSM_ERR_ARG, std::string(E) + ": no polynomial, or lens is null");
+    if ((polys == nullptr) == (d_polys == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of polys (host) / d_polys (device)");
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_fflonk_fold(int group, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys, void *hip_stream,
+                                 uint64_t *out, void *d_out) {
+    VT_OR_FAIL(group);
+    const char *E = "gmsm_fflonk_fold";
+    if ((out == nullptr) == (d_out == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out (host) / d_out (device)");
+    if ((polys && polys == out) || (d_polys && d_polys == d_out))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": the output aliases the input (inputs are never modified)");
+    int rc = fflonk_pack_args(E, polys, d_polys, lens, npolys);
+    if (rc || (rc = vt->fflonk_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
+    Context *ctx;
+    if ((rc = get_context_of_pointer(d_polys ? d_polys : d_out, &ctx))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
+    return vt->fflonk_fold(*ctx, polys, d_polys, lens, npolys, (hipStream_t)hip_stream, out, d_out, nullptr, nullptr);
+}
+
+GMSM_EXPORT int gmsm_fflonk_fold_commit(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys,
+                                        void *hip_stream, void *d_out_folded, uint64_t *out_jac) {
+    const char *E = "gmsm_fflonk_fold_commit";
+    if (!out_jac) return fail(GMSM_ERR_ARG, std::string(E) + ": out_jac is null");
+    if ((polys && polys == out_jac) || (d_polys && d_polys == d_out_folded))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": an output aliases the input (inputs are never modified)");
+    int rc = fflonk_pack_args(E, polys, d_polys, lens, npolys);
+    if (rc) return rc;
+    BasesRef rb = lookup_bases(handle);
+    if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
+    const GroupVTable *vt = vtable(rb->group);
+    if (!vt->fflonk_open_w) return fail(GMSM_ERR_ARG, ERR_FFLONK_G1);
+    if ((rc = vt->fflonk_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
+    size_t t = 0, n = 0;
+    vt->fflonk_next_divisor(npolys, &t);
+    for (size_t j = 0; j < npolys; ++j) n = std::max(n, lens[j]);
+    if (t * n > rb->n) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);  // Commit's size check (kzg.go:159-162) over the folded length
+    Context *ctx;
+    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device)) || (rc = check_device_vector(E, "d_out_folded", d_out_folded, ctx->device)))
+        return rc;
+    return vt->fflonk_fold(*ctx, polys, d_polys, lens, npolys, (hipStream_t)hip_stream, nullptr, d_out_folded, rb.get(), out_jac);
+}
+
+// The checks the two open entries share, in this order: required pointers and pointer pairs (by the callers), the handle, G1,
+// then every refusal that depends on the packs and the points, the size condition last - all on the host - then the device
+// of the bases.
+static int fflonk_open_check(const char *E, uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens,
+                             const size_t *pack_sizes, size_t k, const uint64_t *points, const size_t *npoints, BasesRef *rb_out,
+                             const GroupVTable **vt_out, Context **ctx_out) {
+    if ((polys == nullptr) == (d_polys == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of polys (host) / d_polys (device)");
+    BasesRef rb = lookup_bases(handle);
+    if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
+    const GroupVTable *vt = vtable(rb->group);
+    if (!vt->fflonk_open_w) return fail(GMSM_ERR_ARG, ERR_FFLONK_G1);
+    int rc = vt->fflonk_check(E, lens, pack_sizes, k, points, npoints, true, rb->n);
+    if (rc) return rc;
+    Context *ctx;
+    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
+    *rb_out = rb, *vt_out = vt, *ctx_out = ctx;
+    return GMSM_OK;
+}
+
+static int fflonk_nonempty(const char *E, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points, const size_t *npoints) {
+    if (k == 0 || !lens || !pack_sizes || !npoints || !points)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": no pack of polynomials, or lens / pack_sizes / points / npoints is null");
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_fflonk_open_w(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
+                                   size_t k, const uint64_t *points, const size_t *npoints, const uint64_t *gamma, void *hip_stream,
+                                   uint64_t *out_claimed, uint64_t *out_folded_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_w_jac) {
+    const char *E = "gmsm_fflonk_open_w";
+    if (int rc0 = fflonk_nonempty(E, lens, pack_sizes, k, points, npoints)) return rc0;
+    if (!gamma || !out_claimed || !out_folded_claimed || !out_w_jac)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": gamma, out_claimed, out_folded_claimed and out_w_jac must not be null");
+    if ((out_w == nullptr) == (d_out_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_w (host) / d_out_w (device)");
+    const uint64_t *outs[] = {out_claimed, out_folded_claimed, out_w, out_w_jac};
+    bool alias = d_polys && d_polys == d_out_w;
+    for (int a = 0; a < 4; ++a) {
+        if (!outs[a]) continue;
+        alias = alias || outs[a] == polys || outs[a] == points || outs[a] == gamma;
+        for (int b = a + 1; b < 4; ++b) alias = alias || outs[a] == outs[b];
+    }
+    if (alias) return fail(GMSM_ERR_ARG, std::string(E) + ": an output aliases an input or another output (inputs are never modified)");
+    BasesRef rb;
+    const GroupVTable *vt;
+    Context *ctx;
+    int rc = fflonk_open_check(E, handle, polys, d_polys, lens, pack_sizes, k, points, npoints, &rb, &vt, &ctx);
+    if (rc) return rc;
+    if ((rc = check_device_vector(E, "d_out_w", d_out_w, ctx->device))) return rc;
+    return vt->fflonk_open_w(*ctx, polys, d_polys, lens, pack_sizes, k, points, npoints, gamma, (hipStream_t)hip_stream, out_claimed,
+                             out_folded_claimed, out_w, d_out_w, out_w_jac, rb.get());
+}
+
+GMSM_EXPORT int gmsm_fflonk_open_wprime(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens,
+                                        const size_t *pack_sizes, size_t k, const uint64_t *points, const size_t *npoints,
+                                        const uint64_t *folded_claimed, const uint64_t *gamma, const uint64_t *w, const void *d_w,
+                                        const uint64_t *z, void *hip_stream, uint64_t *out_wprime_jac) {
+    const char *E = "gmsm_fflonk_open_wprime";
+    if (int rc0 = fflonk_nonempty(E, lens, pack_sizes, k, points, npoints)) return rc0;
+    if (!folded_claimed || !gamma || !z || !out_wprime_jac)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": folded_claimed, gamma, z and out_wprime_jac must not be null");
+    if ((w == nullptr) == (d_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of w (host) / d_w (device)");
+    if ((polys && polys == out_wprime_jac) || (w && w == out_wprime_jac) || points == out_wprime_jac || folded_claimed == out_wprime_jac)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": out_wprime_jac aliases an input (inputs are never modified)");
+    BasesRef rb;
+    const GroupVTable *vt;
+    Context *ctx;
+    int rc = fflonk_open_check(E, handle, polys, d_polys, lens, pack_sizes, k, points, npoints, &rb, &vt, &ctx);
+    if (rc) return rc;
+    if ((rc = check_device_vector(E, "d_w", d_w, ctx->device))) return rc;
+    return vt->fflonk_open_wprime(*ctx, polys, d_polys, lens, pack_sizes, k, points, npoints, folded_claimed, gamma, w, d_w, z,
+                                  (hipStream_t)hip_stream, out_wprime_jac, rb.get());
+}
+
 // ------------------------------------------------------------------ ToLagrangeG1 (gmsm_group_fft.h)
 static const char *const ERR_POW2 = "len(coeffs) must be a power of 2";  // ToLagrangeG1, kzg/utils.go
 static const char *const ERR_G1_ONLY = "ToLagrangeG1 is defined for G1 only";

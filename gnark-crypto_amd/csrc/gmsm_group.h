@@ -21,6 +21,7 @@
 #include "gmsm_fft.h"
 #include "gmsm_poly.h"
 #include "gmsm_shplonk.h"
+#include "gmsm_fflonk.h"
 #include "gmsm_group_fft.h"
 
 namespace gmsm {

@@ -390,6 +390,115 @@ struct VTableOf {
         if constexpr (IS_G1) return &shplonk_open_wprime;
         else return nullptr;
     }
+    // ---- fflonk Fold, FoldAndCommit, BatchOpen (gmsm_fflonk.h)
+    using FF = FflonkField<typename G::FrP>;
+    static bool fflonk_next_divisor(size_t n, size_t *t) { return FF::next_divisor(n, t); }
+    static int fflonk_check(const char *E, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
+                            const size_t *npoints, bool check_size, size_t registered) {
+        typename FF::Plan p;
+        return FF::plan(E, lens, pack_sizes, k, points, npoints, check_size, registered, &p);
+    }
+    static size_t fflonk_table_elems(const typename FF::Plan &p) { return ((2 * p.npolys + 3 * p.k) * 8 + sizeof(Fr) - 1) / sizeof(Fr); }
+    static int fflonk_fold(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys, hipStream_t caller,
+                           uint64_t *out, void *d_out, const ResidentBases *resident, uint64_t *out_jac) {
+        typename FF::Plan p;
+        int rc = FF::plan("gmsm_fflonk_fold", lens, &npolys, 1, nullptr, nullptr, false, 0, &p);
+        if (rc) return rc;
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const Fr *in;
+        if ((rc = poly_input(ws, polys, d_polys, p.total, caller, &in))) return rc;
+        if (d_out && polys && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out
+        const size_t head = fflonk_table_elems(p), fbuf = d_out ? 0 : p.maxfold;
+        if ((rc = ws.poly.ensure((head + fbuf) * sizeof(Fr)))) return rc;
+        std::vector<uint64_t> tbl(2 * p.npolys + 3 * p.k);
+        FF::tables(p, lens, tbl.data());
+        Fr *folded = d_out ? (Fr *)d_out : (Fr *)ws.poly.ptr + head;
+        HIP_TRY(hipMemcpyAsync(ws.poly.ptr, tbl.data(), tbl.size() * 8, hipMemcpyHostToDevice, ws.stream));
+        if ((rc = FF::fold(ws.stream, in, (const uint64_t *)ws.poly.ptr, npolys, p.t[0], p.maxfold, folded))) return rc;
+        if (out) HIP_TRY(hipMemcpyAsync(out, folded, p.maxfold * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        typename G::J j{G::F::one(), G::F::one(), G::F::zero()};
+        // the folded polynomial is committed where it is: the resident MultiExp over the folded length
+        if (resident && (rc = G::multiexp_device(ctx, ws, nullptr, folded, p.maxfold, ws.stream, &j, resident))) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));  // `tbl` is pageable host memory: alive until here
+        if (out_jac) memcpy(out_jac, &j, sizeof j);
+        return GMSM_OK;
+    }
+    static int fflonk_open_w(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes, size_t k,
+                             const uint64_t *points, const size_t *npoints, const uint64_t *gamma, hipStream_t caller, uint64_t *out_claimed,
+                             uint64_t *out_folded_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_jac, const ResidentBases *resident) {
+        typename FF::Plan p;
+        int rc = FF::plan("gmsm_fflonk_open_w", lens, pack_sizes, k, points, npoints, true, resident->n, &p);
+        if (rc) return rc;
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const Fr *in;
+        if ((rc = poly_input(ws, polys, d_polys, p.total, caller, &in))) return rc;
+        if (d_out_w && polys && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out_w
+        const size_t wbuf = out_w ? p.maxfold : 0, ping = p.maxmember - 1;
+        const unsigned lanes = PF::lane_option();
+        const size_t scratch_elems = SF::chain_scratch(lens, p.member_points.data(), p.npolys, lanes);
+        if ((rc = ws.poly.ensure((p.nrem + wbuf + 2 * ping + scratch_elems) * sizeof(Fr)))) return rc;
+        Fr *rem = (Fr *)ws.poly.ptr, *w = out_w ? rem + p.nrem : (Fr *)d_out_w, *a = rem + p.nrem + wbuf, *b = a + ping, *scratch = b + ping;
+        Fr g;
+        memcpy(&g, gamma, sizeof g);
+        if ((rc = FF::chains(ws.stream, p, in, lens, g, rem, w, a, b, scratch, lanes))) return rc;
+        std::vector<Fr> d(p.nrem);
+        HIP_TRY(hipMemcpyAsync(d.data(), rem, p.nrem * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        if (out_w) HIP_TRY(hipMemcpyAsync(out_w, w, p.maxfold * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        // w is committed where it is: the resident MultiExp over its true length
+        const typename G::J j = commit_or_infinity(ctx, ws, w, p.wlen, resident, &rc);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        FF::claimed_values(p, d.data(), (Fr *)out_claimed, (Fr *)out_folded_claimed);
+        memcpy(out_jac, &j, sizeof j);
+        return GMSM_OK;
+    }
+    static int fflonk_open_wprime(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
+                                  size_t k, const uint64_t *points, const size_t *npoints, const uint64_t *folded_claimed,
+                                  const uint64_t *gamma, const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t caller,
+                                  uint64_t *out_jac, const ResidentBases *resident) {
+        typename FF::Plan p;
+        int rc = FF::plan("gmsm_fflonk_open_wprime", lens, pack_sizes, k, points, npoints, true, resident->n, &p);
+        if (rc) return rc;
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const Fr *in;
+        if ((rc = poly_input(ws, polys, d_polys, p.total, caller, &in))) return rc;
+        if (d_w && polys && (rc = order_after(ws, caller))) return rc;  // d_w is the caller's stream's
+        // host part: shplonk's c_i, Z_T(z), sum_i c_i r_i(z) over the extended sets and the inner claimed values, then the
+        // index tables, in one staging vector of Fr-sized slots
+        const size_t head = k + 2 + fflonk_table_elems(p);
+        std::vector<Fr> stage(head);
+        Fr g, zz;
+        memcpy(&g, gamma, sizeof g);
+        memcpy(&zz, z, sizeof zz);
+        SF::combine_coefficients(p.ext.data(), p.ext_npoints.data(), k, (const Fr *)folded_claimed, g, zz, stage.data());
+        FF::tables(p, lens, (uint64_t *)(stage.data() + k + 2));
+        const size_t n = p.maxfold, wbuf = w ? n : 0;
+        const unsigned lanes = PF::lane_option();
+        if ((rc = ws.poly.ensure((head + wbuf + n + (n - 1) + PF::scratch_elems(n, lanes)) * sizeof(Fr)))) return rc;
+        Fr *coef = (Fr *)ws.poly.ptr, *wdev = coef + head, *l = wdev + wbuf, *h = l + n, *scratch = h + (n - 1);
+        HIP_TRY(hipMemcpyAsync(coef, stage.data(), head * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+        if (w) HIP_TRY(hipMemcpyAsync(wdev, w, n * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+        const Fr *wsrc = w ? wdev : (const Fr *)d_w;
+        if ((rc = FF::combine(ws.stream, p, in, (const uint64_t *)(coef + k + 2), coef, wsrc, l))) return rc;
+        // L(z) = 0 for true claimed values; the quotient does not depend on the remainder either way
+        if (n > 1 && (rc = PF::suffix(ws.stream, PF::powers_of(z), l, n, h, nullptr, scratch, lanes))) return rc;
+        const typename G::J j = commit_or_infinity(ctx, ws, h, n - 1, resident, &rc);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));  // `stage` is pageable host memory: alive until here
+        memcpy(out_jac, &j, sizeof j);
+        return GMSM_OK;
+    }
+    static constexpr decltype(GroupVTable::fflonk_open_w) fflonk_w_entry() {
+        if constexpr (IS_G1) return &fflonk_open_w;
+        else return nullptr;
+    }
+    static constexpr decltype(GroupVTable::fflonk_open_wprime) fflonk_wprime_entry() {
+        if constexpr (IS_G1) return &fflonk_open_wprime;
+        else return nullptr;
+    }
     // ---- ToLagrangeG1 (gmsm_group_fft.h)
     static int to_lagrange(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
                            hipStream_t caller, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases) {
@@ -427,6 +536,7 @@ struct VTableOf {
                                        &fold,           &jac_to_affine, &debug_decompose, &debug_field_op,
                                        &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info,
                                        &poly_eval, &poly_div, &kzg_open, lagrange_entry(), shplonk_w_entry(), shplonk_wprime_entry(),
+                                       &fflonk_next_divisor, &fflonk_check, &fflonk_fold, fflonk_w_entry(), fflonk_wprime_entry(),
                                        (unsigned)G::FrP::MAX_ORDER};
         return &vt;
     }

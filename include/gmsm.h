@@ -325,6 +325,50 @@ int gmsm_shplonk_open_wprime(uint64_t handle, const uint64_t *polys, const void 
                              const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
                              const uint64_t *w, const void *d_w, const uint64_t *z, void *hip_stream, uint64_t *out_wprime_jac);
 
+/* ---- fflonk (ecc/<curve>/fflonk/fflonk.go:41-141) over registered G1 bases: Fold, FoldAndCommit and the two halves of
+ *      BatchOpen, which opens packs of polynomials. A pack of c polynomials is interleaved into one,
+ *      Fold = sum_(j<t) P_j(X^t) X^j with t = getNextDivisorRMinusOne(c) (fflonk.go:234-252: the smallest divisor of r - 1
+ *      that is >= c, at most 100 trials; P_j = 0 for c <= j < t), and opened by shplonk on the orbit {z, wz, .., w^(t-1) z}
+ *      of each of its base points, w = g^((r-1)/t) with g the generator gmsm_fft_domain_info reports. Results are
+ *      bit-identical to the reference's. Packs: all polynomials of all k packs concatenated (fr.Element vectors), lens[] one
+ *      entry per polynomial, pack_sizes[k] each pack's polynomial count; exactly one of a host pointer / a 16-byte aligned
+ *      device pointer produced on hip_stream, never modified. An empty member (lens == 0) of a non-empty pack is the zero
+ *      polynomial. `points` holds sum_i npoints[i] BASE points on the host, pack after pack. Every call returns when its
+ *      results are complete; scratch comes from the workspace of the call.
+ *   gmsm_fflonk_next_divisor: t for n polynomials over the group's scalar field; host only.
+ *   gmsm_fflonk_fold: Fold of one pack, t * max_j lens[j] elements to exactly one of out (host) / d_out (device).
+ *   gmsm_fflonk_fold_commit: out_jac = Commit(Fold(pack)) as Jacobian {X,Y,Z} through the resident MultiExp over the folded
+ *      length (an all-zero fold commits to infinity); the folded polynomial also goes to d_out_folded when that is not NULL.
+ *   gmsm_fflonk_open_w (given gamma): with n_i = max length in pack i, a_k = z_k^t_i:
+ *      out_claimed = ClaimedValues[i][j][k] = P_j(a_k): pack after pack t_i rows of npoints[i] values, rows j >= pack_sizes[i] zero;
+ *      out_folded_claimed = SOpeningProof.ClaimedValues[i][k t_i + l] = Fold_i(w^l z_k): sum_i t_i npoints[i] elements;
+ *      w = shplonk's w over the folded polynomials and the extended sets, computed as sum_i gamma^i Fold_i(P_j div
+ *      prod_k (Y - a_k)) - t_i chains of npoints[i] divisions over n_i coefficients instead of one chain of t_i npoints[i]
+ *      divisions over t_i n_i - to exactly one of out_w (host) / d_out_w (device): max_i t_i n_i elements, zero above the
+ *      true degree; out_w_jac = Commit(w).
+ *   gmsm_fflonk_open_wprime (given z): out_wprime_jac = Commit(L / (X - z)), L as for gmsm_shplonk_open_wprime over the
+ *      folded polynomials (read from the packs in place, no folded copy), the extended sets, folded_claimed (the layout
+ *      of out_folded_claimed) and w (max_i t_i n_i elements) from exactly one of w (host) / d_w (device).
+ *   Errors, all GMSM_ERR_ARG with a text, all before any device work: k == 0 or a null required pointer; both or none of a
+ *   pair of pointers; an unknown handle or a handle of G2 bases; pack_sizes[i] == 0; no divisor within 100 trials;
+ *   npoints[i] == 0; a pack whose members are all empty (the folded polynomial is empty); two equal points in an extended
+ *   set - z_a^t = z_b^t for a != b, or z = 0 with t_i > 1 (z = 0 with t_i = 1 is legal) - where the reference inverts zero;
+ *   and shplonk's size condition over the FOLDED sizes, checked up front in both open entries: lengths t_i n_i and set sizes
+ *   t_i npoints[i] in the condition of gmsm_shplonk_open_w - "invalid polynomial size (larger than SRS or == 0)", which
+ *   gmsm_fflonk_fold_commit also returns for a fold longer than the registered size. ---- */
+int gmsm_fflonk_next_divisor(int group, size_t n, size_t *out_t);
+int gmsm_fflonk_fold(int group, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys, void *hip_stream,
+                     uint64_t *out, void *d_out);
+int gmsm_fflonk_fold_commit(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys,
+                            void *hip_stream, void *d_out_folded, uint64_t *out_jac);
+int gmsm_fflonk_open_w(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
+                       size_t k, const uint64_t *points, const size_t *npoints, const uint64_t *gamma, void *hip_stream,
+                       uint64_t *out_claimed, uint64_t *out_folded_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_w_jac);
+int gmsm_fflonk_open_wprime(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
+                            size_t k, const uint64_t *points, const size_t *npoints, const uint64_t *folded_claimed,
+                            const uint64_t *gamma, const uint64_t *w, const void *d_w, const uint64_t *z, void *hip_stream,
+                            uint64_t *out_wprime_jac);
+
 /* ---- ToLagrangeG1 (ecc/<curve>/kzg/utils.go:25-64): the Lagrange form of an SRS, out[i] = (1/n) sum_j w^(-ij) P_j with
  *      w = fr.Generator(n) - for P_j = [tau^j]G that is [L_i(tau)]G - as an inverse FFT over G1 points on the device
  *      (gmsm_group_fft.h). Results are canonical affine limbs (infinity = (0, 0)), bit-identical to the reference's.
