@@ -705,35 +705,29 @@ struct GroupVTable {
     // registration `out_bases`. nullptr for the G2 groups.
     int (*to_lagrange)(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
                        hipStream_t stream, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases);
-    // shplonk.BatchOpen over registered G1 bases (gmsm_shplonk.h): polynomials as for kzg_open; `points` holds the sets S_i one
-    // after the other (npoints[i] elements each, host), `claimed` the values in the same layout. nullptr for the G2 groups.
-    //   open_w: out_claimed, w = sum_i gamma^i (f_i div Z_(S_i)) (maxlen elements) to out_w (host) or d_out_w (device), W = Commit(w)
-    //   open_wprime: W' = Commit((sum_i c_i f_i - sum_i c_i r_i(z) - Z_T(z) w) / (X - z)), w from the host or the device
-    int (*shplonk_open_w)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *points,
-                          const size_t *npoints, const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed, uint64_t *out_w,
-                          void *d_out_w, uint64_t *out_jac, const ResidentBases *resident);
-    int (*shplonk_open_wprime)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
-                               const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
-                               const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t stream, uint64_t *out_jac,
-                               const ResidentBases *resident);
-    // fflonk (gmsm_fflonk.h). Packs: all polynomials of all k packs concatenated, lens[] per polynomial, pack_sizes[] per pack.
+    // shplonk and fflonk over registered G1 bases (gmsm_fflonk.h, gmsm_shplonk.h): polynomials as for kzg_open, all polynomials
+    // of all k packs concatenated, lens[] per polynomial, pack_sizes[] per pack; `points` holds the k sets one after the other
+    // (npoints[i] elements each, host). pack_sizes == null is shplonk: k polynomials, each opened on its own set.
     //   fflonk_next_divisor: getNextDivisorRMinusOne over the group's scalar field, host only; false when there is none
-    //   fflonk_check: every refusal that depends on the packs and the points (points == null: the packs alone), host only;
-    //                 `registered` bases for the size condition of the two open entries (check_size)
+    //   open_check: every refusal that depends on the packs and the points (points == null: the packs alone), host only;
+    //               `registered` bases for the size condition of the open entries (check_size)
     //   fflonk_fold: Fold of one pack to out (host) / d_out (device) / the workspace (both null), and with `resident` its Commit
-    //   fflonk_open_w / fflonk_open_wprime: the two halves of fflonk.BatchOpen; nullptr for the G2 groups
+    //   open_w: the claimed values (shplonk: out_claimed in the layout of points, out_folded_claimed unused; fflonk: both
+    //           sets), w (max_i t_i n_i elements) to out_w (host) or d_out_w (device), W = Commit(w)
+    //   open_wprime: W' = Commit((sum_i c_i F_i - sum_i c_i r_i(z) - Z_T(z) w) / (X - z)) from shplonk's claimed values (for
+    //                fflonk the folded ones), w from the host or the device. Both nullptr for the G2 groups.
     bool (*fflonk_next_divisor)(size_t n, size_t *t);
-    int (*fflonk_check)(const char *entry, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
-                        const size_t *npoints, bool check_size, size_t registered);
+    int (*open_check)(const char *entry, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
+                      const size_t *npoints, bool check_size, size_t registered);
     int (*fflonk_fold)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys, hipStream_t stream,
                        uint64_t *out, void *d_out, const ResidentBases *resident, uint64_t *out_jac);
-    int (*fflonk_open_w)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes, size_t k,
-                         const uint64_t *points, const size_t *npoints, const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed,
-                         uint64_t *out_folded_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_jac, const ResidentBases *resident);
-    int (*fflonk_open_wprime)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
-                              size_t k, const uint64_t *points, const size_t *npoints, const uint64_t *folded_claimed,
-                              const uint64_t *gamma, const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t stream,
-                              uint64_t *out_jac, const ResidentBases *resident);
+    int (*open_w)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes, size_t k,
+                  const uint64_t *points, const size_t *npoints, const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed,
+                  uint64_t *out_folded_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_jac, const ResidentBases *resident);
+    int (*open_wprime)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes, size_t k,
+                       const uint64_t *points, const size_t *npoints, const uint64_t *folded_claimed, const uint64_t *gamma,
+                       const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t stream, uint64_t *out_jac,
+                       const ResidentBases *resident);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

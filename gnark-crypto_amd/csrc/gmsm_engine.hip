@@ -1418,45 +1418,35 @@ GMSM_EXPORT int gmsm_kzg_open_folded(uint64_t handle, const uint64_t *polys, con
     return kzg_open_impl("gmsm_kzg_open_folded", handle, polys, d_polys, lens, k, point, gamma, hip_stream, nullptr, out_h_jac);
 }
 
-// ------------------------------------------------------------------ shplonk.BatchOpen (gmsm_shplonk.h)
+// ------------------------------------------------------------------ shplonk.BatchOpen, fflonk.BatchOpen (gmsm_fflonk.h)
 static const char *const ERR_SHPLONK_G1 = "shplonk opens over G1 bases only";
+static const char *const ERR_FFLONK_G1 = "fflonk commits and opens over G1 bases only";
 
-// The checks both entries share (shplonk.go:44-83 and Commit's size check, kzg.go:159-162), then the device of the bases.
-// maxSizePolys = max(max_i lens[i], max_i npoints[i] + 1); Commit(wPrime) runs over maxSizePolys + sum_i npoints[i] - 1
-// coefficients in the reference, so that many bases must be registered (the device MSMs run over true lengths only).
-static int shplonk_nonempty(const char *E, const size_t *lens, size_t k, const uint64_t *points, const size_t *npoints) {
-    if (k == 0 || !lens || !npoints || !points) return fail(GMSM_ERR_ARG, std::string(E) + ": no polynomial, or lens / points / npoints is null");
+// The four open entries take shplonk's k polynomials (pack_sizes is no argument of theirs: null from here on) or fflonk's k
+// packs. Their checks, in this order: the counts and arrays (open_nonempty), the entry's own pointers and aliases, then
+// open_check: the polynomials' pointer pair, the handle, G1, every refusal that depends on the polynomials and the points
+// (GroupVTable::open_check: shplonk.go:44-83, fflonk.go:77-141), the size condition last - the reference commits w' over
+// maxSizePolys + sum_i npoints[i] - 1 coefficients, so that many bases must be registered although the device MSMs run over
+// true lengths only (kzg.go:159-162) - all on the host, then the device of the bases.
+static int open_nonempty(const char *E, bool packed, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
+                         const size_t *npoints) {
+    if (k == 0 || !lens || (packed && !pack_sizes) || !npoints || !points)
+        return fail(GMSM_ERR_ARG, std::string(E) + (packed ? ": no pack of polynomials, or lens / pack_sizes / points / npoints is null"
+                                                           : ": no polynomial, or lens / points / npoints is null"));
     return GMSM_OK;
 }
 
-static int shplonk_check(const char *E, uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
-                         const uint64_t *points, const size_t *npoints, BasesRef *rb_out, const GroupVTable **vt_out, Context **ctx_out) {
+static int open_check(const char *E, uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
+                      size_t k, const uint64_t *points, const size_t *npoints, BasesRef *rb_out, const GroupVTable **vt_out, Context **ctx_out) {
     if ((polys == nullptr) == (d_polys == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of polys (host) / d_polys (device)");
     BasesRef rb = lookup_bases(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
-    if (!vt->shplonk_open_w) return fail(GMSM_ERR_ARG, ERR_SHPLONK_G1);
-    size_t max_size = 0, total_points = 0;
-    for (size_t i = 0; i < k; ++i) {
-        if (lens[i] == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": polynomial " + std::to_string(i) + " is empty (eval reads p[len(p)-1])");
-        if (npoints[i] == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": polynomial " + std::to_string(i) + " has no opening point");
-        max_size = std::max(max_size, std::max(lens[i], npoints[i] + 1));
-        total_points += npoints[i];
-    }
-    // equal points inside one set: the reference's interpolate inverts zero there (shplonk.go:406-415) and returns a
-    // meaningless proof without an error; refused here. Elements are canonical, so equal values have equal limbs.
-    const size_t sb = vt->scalar_bytes;
-    const unsigned char *pt = (const unsigned char *)points;
-    for (size_t i = 0, p = 0; i < k; p += npoints[i], ++i)
-        for (size_t a = 0; a < npoints[i]; ++a)
-            for (size_t b = a + 1; b < npoints[i]; ++b)
-                if (memcmp(pt + (p + a) * sb, pt + (p + b) * sb, sb) == 0)
-                    return fail(GMSM_ERR_ARG, std::string(E) + ": set " + std::to_string(i) + " holds the same point twice (points " +
-                                                  std::to_string(a) + " and " + std::to_string(b) + ")");
-    if (max_size + total_points - 1 > rb->n) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);
-    Context *ctx;
-    int rc = get_context_for(rb->device, &ctx);  // the bases decide the device
+    if (!vt->open_w) return fail(GMSM_ERR_ARG, pack_sizes ? ERR_FFLONK_G1 : ERR_SHPLONK_G1);
+    int rc = vt->open_check(E, lens, pack_sizes, k, points, npoints, true, rb->n);
     if (rc) return rc;
+    Context *ctx;
+    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
     *rb_out = rb, *vt_out = vt, *ctx_out = ctx;
@@ -1467,7 +1457,7 @@ GMSM_EXPORT int gmsm_shplonk_open_w(uint64_t handle, const uint64_t *polys, cons
                                     const uint64_t *points, const size_t *npoints, const uint64_t *gamma, void *hip_stream,
                                     uint64_t *out_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_w_jac) {
     const char *E = "gmsm_shplonk_open_w";
-    if (int rc0 = shplonk_nonempty(E, lens, k, points, npoints)) return rc0;
+    if (int rc0 = open_nonempty(E, false, lens, nullptr, k, points, npoints)) return rc0;
     if (!gamma || !out_claimed || !out_w_jac) return fail(GMSM_ERR_ARG, std::string(E) + ": gamma, out_claimed and out_w_jac must not be null");
     if ((out_w == nullptr) == (d_out_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_w (host) / d_out_w (device)");
     if ((polys && (polys == out_w || polys == out_claimed || polys == out_w_jac)) || (d_polys && d_polys == d_out_w) || out_claimed == out_w ||
@@ -1476,18 +1466,18 @@ GMSM_EXPORT int gmsm_shplonk_open_w(uint64_t handle, const uint64_t *polys, cons
     BasesRef rb;
     const GroupVTable *vt;
     Context *ctx;
-    int rc = shplonk_check(E, handle, polys, d_polys, lens, k, points, npoints, &rb, &vt, &ctx);
+    int rc = open_check(E, handle, polys, d_polys, lens, nullptr, k, points, npoints, &rb, &vt, &ctx);
     if (rc) return rc;
     if ((rc = check_device_vector(E, "d_out_w", d_out_w, ctx->device))) return rc;
-    return vt->shplonk_open_w(*ctx, polys, d_polys, lens, k, points, npoints, gamma, (hipStream_t)hip_stream, out_claimed, out_w, d_out_w,
-                              out_w_jac, rb.get());
+    return vt->open_w(*ctx, polys, d_polys, lens, nullptr, k, points, npoints, gamma, (hipStream_t)hip_stream, out_claimed, nullptr, out_w,
+                      d_out_w, out_w_jac, rb.get());
 }
 
 GMSM_EXPORT int gmsm_shplonk_open_wprime(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
                                          const uint64_t *points, const size_t *npoints, const uint64_t *claimed, const uint64_t *gamma,
                                          const uint64_t *w, const void *d_w, const uint64_t *z, void *hip_stream, uint64_t *out_wprime_jac) {
     const char *E = "gmsm_shplonk_open_wprime";
-    if (int rc0 = shplonk_nonempty(E, lens, k, points, npoints)) return rc0;
+    if (int rc0 = open_nonempty(E, false, lens, nullptr, k, points, npoints)) return rc0;
     if (!claimed || !gamma || !z || !out_wprime_jac)
         return fail(GMSM_ERR_ARG, std::string(E) + ": claimed, gamma, z and out_wprime_jac must not be null");
     if ((w == nullptr) == (d_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of w (host) / d_w (device)");
@@ -1496,15 +1486,14 @@ GMSM_EXPORT int gmsm_shplonk_open_wprime(uint64_t handle, const uint64_t *polys,
     BasesRef rb;
     const GroupVTable *vt;
     Context *ctx;
-    int rc = shplonk_check(E, handle, polys, d_polys, lens, k, points, npoints, &rb, &vt, &ctx);
+    int rc = open_check(E, handle, polys, d_polys, lens, nullptr, k, points, npoints, &rb, &vt, &ctx);
     if (rc) return rc;
     if ((rc = check_device_vector(E, "d_w", d_w, ctx->device))) return rc;
-    return vt->shplonk_open_wprime(*ctx, polys, d_polys, lens, k, points, npoints, claimed, gamma, w, d_w, z, (hipStream_t)hip_stream,
-                                   out_wprime_jac, rb.get());
+    return vt->open_wprime(*ctx, polys, d_polys, lens, nullptr, k, points, npoints, claimed, gamma, w, d_w, z, (hipStream_t)hip_stream,
+                           out_wprime_jac, rb.get());
 }
 
 // ------------------------------------------------------------------ fflonk Fold, FoldAndCommit, BatchOpen (gmsm_fflonk.h)
-static const char *const ERR_FFLONK_G1 = "fflonk commits and opens over G1 bases only";
 
 GMSM_EXPORT int gmsm_fflonk_next_divisor(int group, size_t n, size_t *out_t) {
     VT_OR_FAIL(group);
@@ -1531,7 +1520,7 @@ GMSM_EXPORT int gmsm_fflonk_fold(int group, const uint64_t *polys, const void *d
     if ((polys && polys == out) || (d_polys && d_polys == d_out))
         return fail(GMSM_ERR_ARG, std::string(E) + ": the output aliases the input (inputs are never modified)");
     int rc = fflonk_pack_args(E, polys, d_polys, lens, npolys);
-    if (rc || (rc = vt->fflonk_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
+    if (rc || (rc = vt->open_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
     Context *ctx;
     if ((rc = get_context_of_pointer(d_polys ? d_polys : d_out, &ctx))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1550,8 +1539,8 @@ GMSM_EXPORT int gmsm_fflonk_fold_commit(uint64_t handle, const uint64_t *polys, 
     BasesRef rb = lookup_bases(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
-    if (!vt->fflonk_open_w) return fail(GMSM_ERR_ARG, ERR_FFLONK_G1);
-    if ((rc = vt->fflonk_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
+    if (!vt->open_w) return fail(GMSM_ERR_ARG, ERR_FFLONK_G1);
+    if ((rc = vt->open_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
     size_t t = 0, n = 0;
     vt->fflonk_next_divisor(npolys, &t);
     for (size_t j = 0; j < npolys; ++j) n = std::max(n, lens[j]);
@@ -1564,38 +1553,11 @@ GMSM_EXPORT int gmsm_fflonk_fold_commit(uint64_t handle, const uint64_t *polys, 
     return vt->fflonk_fold(*ctx, polys, d_polys, lens, npolys, (hipStream_t)hip_stream, nullptr, d_out_folded, rb.get(), out_jac);
 }
 
-// The checks the two open entries share, in this order: required pointers and pointer pairs (by the callers), the handle, G1,
-// then every refusal that depends on the packs and the points, the size condition last - all on the host - then the device
-// of the bases.
-static int fflonk_open_check(const char *E, uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens,
-                             const size_t *pack_sizes, size_t k, const uint64_t *points, const size_t *npoints, BasesRef *rb_out,
-                             const GroupVTable **vt_out, Context **ctx_out) {
-    if ((polys == nullptr) == (d_polys == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of polys (host) / d_polys (device)");
-    BasesRef rb = lookup_bases(handle);
-    if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
-    const GroupVTable *vt = vtable(rb->group);
-    if (!vt->fflonk_open_w) return fail(GMSM_ERR_ARG, ERR_FFLONK_G1);
-    int rc = vt->fflonk_check(E, lens, pack_sizes, k, points, npoints, true, rb->n);
-    if (rc) return rc;
-    Context *ctx;
-    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
-    HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
-    *rb_out = rb, *vt_out = vt, *ctx_out = ctx;
-    return GMSM_OK;
-}
-
-static int fflonk_nonempty(const char *E, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points, const size_t *npoints) {
-    if (k == 0 || !lens || !pack_sizes || !npoints || !points)
-        return fail(GMSM_ERR_ARG, std::string(E) + ": no pack of polynomials, or lens / pack_sizes / points / npoints is null");
-    return GMSM_OK;
-}
-
 GMSM_EXPORT int gmsm_fflonk_open_w(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
                                    size_t k, const uint64_t *points, const size_t *npoints, const uint64_t *gamma, void *hip_stream,
                                    uint64_t *out_claimed, uint64_t *out_folded_claimed, uint64_t *out_w, void *d_out_w, uint64_t *out_w_jac) {
     const char *E = "gmsm_fflonk_open_w";
-    if (int rc0 = fflonk_nonempty(E, lens, pack_sizes, k, points, npoints)) return rc0;
+    if (int rc0 = open_nonempty(E, true, lens, pack_sizes, k, points, npoints)) return rc0;
     if (!gamma || !out_claimed || !out_folded_claimed || !out_w_jac)
         return fail(GMSM_ERR_ARG, std::string(E) + ": gamma, out_claimed, out_folded_claimed and out_w_jac must not be null");
     if ((out_w == nullptr) == (d_out_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_w (host) / d_out_w (device)");
@@ -1610,11 +1572,11 @@ GMSM_EXPORT int gmsm_fflonk_open_w(uint64_t handle, const uint64_t *polys, const
     BasesRef rb;
     const GroupVTable *vt;
     Context *ctx;
-    int rc = fflonk_open_check(E, handle, polys, d_polys, lens, pack_sizes, k, points, npoints, &rb, &vt, &ctx);
+    int rc = open_check(E, handle, polys, d_polys, lens, pack_sizes, k, points, npoints, &rb, &vt, &ctx);
     if (rc) return rc;
     if ((rc = check_device_vector(E, "d_out_w", d_out_w, ctx->device))) return rc;
-    return vt->fflonk_open_w(*ctx, polys, d_polys, lens, pack_sizes, k, points, npoints, gamma, (hipStream_t)hip_stream, out_claimed,
-                             out_folded_claimed, out_w, d_out_w, out_w_jac, rb.get());
+    return vt->open_w(*ctx, polys, d_polys, lens, pack_sizes, k, points, npoints, gamma, (hipStream_t)hip_stream, out_claimed,
+                      out_folded_claimed, out_w, d_out_w, out_w_jac, rb.get());
 }
 
 GMSM_EXPORT int gmsm_fflonk_open_wprime(uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens,
@@ -1622,7 +1584,7 @@ GMSM_EXPORT int gmsm_fflonk_open_wprime(uint64_t handle, const uint64_t *polys, 
                                         const uint64_t *folded_claimed, const uint64_t *gamma, const uint64_t *w, const void *d_w,
                                         const uint64_t *z, void *hip_stream, uint64_t *out_wprime_jac) {
     const char *E = "gmsm_fflonk_open_wprime";
-    if (int rc0 = fflonk_nonempty(E, lens, pack_sizes, k, points, npoints)) return rc0;
+    if (int rc0 = open_nonempty(E, true, lens, pack_sizes, k, points, npoints)) return rc0;
     if (!folded_claimed || !gamma || !z || !out_wprime_jac)
         return fail(GMSM_ERR_ARG, std::string(E) + ": folded_claimed, gamma, z and out_wprime_jac must not be null");
     if ((w == nullptr) == (d_w == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of w (host) / d_w (device)");
@@ -1631,11 +1593,11 @@ GMSM_EXPORT int gmsm_fflonk_open_wprime(uint64_t handle, const uint64_t *polys, 
     BasesRef rb;
     const GroupVTable *vt;
     Context *ctx;
-    int rc = fflonk_open_check(E, handle, polys, d_polys, lens, pack_sizes, k, points, npoints, &rb, &vt, &ctx);
+    int rc = open_check(E, handle, polys, d_polys, lens, pack_sizes, k, points, npoints, &rb, &vt, &ctx);
     if (rc) return rc;
     if ((rc = check_device_vector(E, "d_w", d_w, ctx->device))) return rc;
-    return vt->fflonk_open_wprime(*ctx, polys, d_polys, lens, pack_sizes, k, points, npoints, folded_claimed, gamma, w, d_w, z,
-                                  (hipStream_t)hip_stream, out_wprime_jac, rb.get());
+    return vt->open_wprime(*ctx, polys, d_polys, lens, pack_sizes, k, points, npoints, folded_claimed, gamma, w, d_w, z,
+                           (hipStream_t)hip_stream, out_wprime_jac, rb.get());
 }
 
 // ------------------------------------------------------------------ ToLagrangeG1 (gmsm_group_fft.h)

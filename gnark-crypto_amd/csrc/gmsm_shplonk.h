@@ -1,5 +1,5 @@
-// shplonk.BatchOpen on the device (ecc/<curve>/shplonk/shplonk.go:44-172): polynomial i is opened on its own set of points
-// S_i (m_i of them), T = the concatenation of the sets. The reference forms, over full-length vectors on the host,
+// shplonk.BatchOpen (ecc/<curve>/shplonk/shplonk.go:44-172): polynomial i is opened on its own set of points S_i (m_i of
+// them), T = the concatenation of the sets. The reference forms, over full-length vectors on the host,
 //   w  = (sum_i gamma^i Z_(T\S_i) (f_i - r_i)) / Z_T            r_i = the interpolant of f_i on S_i   (:97-120)
 //   w' = (sum_i c_i (f_i - r_i(z)) - Z_T(z) w) / (X - z)        c_i = gamma^i Z_(T\S_i)(z)            (:132-164)
 // with a naive product by Z_(T\S_i) and a naive division by Z_T. The same results without those products:
@@ -9,40 +9,15 @@
 //   q_(i,j-1)(s_(i,j)) are the Newton coefficients of r_i = d_1 + d_2 (X - s_1) + d_3 (X - s_1)(X - s_2) + ..., so the
 //   claimed values f_i(s_(i,j)) = r_i(s_(i,j)) are a host evaluation of that form: no further pass over f_i.
 //   L = sum_i c_i f_i - (sum_i c_i r_i(z)) - Z_T(z) w in one pass, w' = L div (X - z) in one scan.
-// Every output is a uniquely determined element of Fr in canonical Montgomery form, so the results are the reference's
-// bit for bit. The scalars that depend on the points only (gamma^i, Z_(T\S_i)(z), Z_T(z), r_i(z), the claimed values) are
-// O((sum_i m_i)^2) field operations on the host; nothing on the host touches the coefficient vectors.
-// Launches only: no flag, spin or grid barrier between workgroups.
+// This header holds the host arithmetic of that formulation: the scalars that depend on the points only (gamma^i,
+// Z_(T\S_i)(z), Z_T(z), r_i(z), the claimed values), O((sum_i m_i)^2) field operations, none of which touches a coefficient
+// vector. The device part - chains, accumulation, L - is the opening pipeline of gmsm_fflonk.h, which shplonk enters as
+// the opening whose packs hold one polynomial each (t_i = 1).
 #pragma once
 #include <vector>
 #include "gmsm_poly.h"
 
 namespace gmsm {
-
-// w_j += c q_j for j < n (the accumulation w += gamma^i q_i; w is zero-filled to the longest polynomial beforehand)
-template <class FrP>
-__global__ void __launch_bounds__(256) k_shplonk_accumulate(Fp<FrP> *__restrict__ w, const Fp<FrP> *__restrict__ q, size_t n, Fp<FrP> c) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    fft_store(w, j, fp_add(fft_load(w, j), fp_mul(fft_load(q, j), c)));
-}
-
-// L_j = sum_i c_i f_(i,j) - c_w w_j for j < maxlen (f_(i,j) = 0 for j >= len_i), less the constant at j = 0.
-// off_len: k pairs (offset of polynomial i in polys, its length), in elements. coef: c_0 .. c_(k-1), c_w, the constant.
-template <class FrP>
-__global__ void __launch_bounds__(256) k_shplonk_combine(const Fp<FrP> *__restrict__ polys, const uint64_t *__restrict__ off_len, size_t k,
-                                                         size_t maxlen, const Fp<FrP> *__restrict__ coef, const Fp<FrP> *__restrict__ w,
-                                                         Fp<FrP> *__restrict__ out) {
-    using Fr = Fp<FrP>;
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= maxlen) return;
-    Fr acc = fp_neg(fp_mul(fft_load(w, j), fft_load(coef, k)));
-#pragma nounroll
-    for (size_t i = 0; i < k; ++i)
-        if (j < off_len[2 * i + 1]) acc = fp_add(acc, fp_mul(fft_load(polys, off_len[2 * i] + j), fft_load(coef, i)));
-    if (j == 0) acc = fp_sub(acc, fft_load(coef, k + 1));
-    fft_store(out, j, acc);
-}
 
 // ------------------------------------------------------------------ host side of one scalar field
 template <class FrP>
@@ -68,35 +43,6 @@ struct ShplonkField {
         for (size_t i = 0; i < k; ++i)
             for (size_t j = 0; j < npoints[i] && j < lens[i]; ++j) s = std::max(s, PF::scratch_elems(lens[i] - j, lanes));
         return s;
-    }
-
-    // The chains and the accumulation on `stream`: rem (sum_i m_i elements, device) receives d_(i,j), w (maxlen elements,
-    // device) sum_i gamma^i q_i. a, b: ping-pong vectors of maxlen - 1 elements; scratch: chain_scratch elements for the same
-    // lanes (the call's PolyField::lane_option()).
-    static int chains(hipStream_t stream, const Fr *polys, const size_t *lens, size_t k, const Fr *points, const size_t *npoints,
-                      const Fr &gamma, size_t maxlen, Fr *rem, Fr *w, Fr *a, Fr *b, Fr *scratch, unsigned lanes) {
-        size_t total_points = 0;
-        for (size_t i = 0; i < k; ++i) total_points += npoints[i];
-        HIP_TRY(hipMemsetAsync(rem, 0, total_points * sizeof(Fr), stream));  // a chain that runs out of coefficients leaves d = 0
-        HIP_TRY(hipMemsetAsync(w, 0, maxlen * sizeof(Fr), stream));
-        Fr acc_gamma = Fr::one();
-        int rc;
-        for (size_t i = 0, off = 0, p = 0; i < k; off += lens[i], p += npoints[i], ++i) {
-            const Fr *cur = polys + off;
-            size_t n = lens[i];
-            for (size_t j = 0; j < npoints[i] && n > 0; ++j, --n) {
-                Fr *dst = (j & 1) ? b : a;
-                if ((rc = PF::suffix(stream, FftField<FrP>::powers_of(points[p + j]), cur, n, n > 1 ? dst : nullptr, rem + p + j, scratch, lanes)))
-                    return rc;
-                cur = dst;
-            }
-            if (n > 0) {
-                hipLaunchKernelGGL((k_shplonk_accumulate<FrP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, cur, n, acc_gamma);
-                HIP_TRY(hipGetLastError());
-            }
-            acc_gamma = fp_mul(acc_gamma, gamma);
-        }
-        return GMSM_OK;
     }
 
     // claimed values f_i(s_(i,j)) from the chain's remainders (both sum_i m_i elements, the layout of points)
@@ -132,14 +78,6 @@ struct ShplonkField {
         for (size_t i = 0; i < k; ++i) zt = fp_mul(zt, zs[i]);
         coef[k] = zt;
         coef[k + 1] = sum;
-    }
-
-    static int combine(hipStream_t stream, const Fr *polys, const uint64_t *off_len, size_t k, size_t maxlen, const Fr *coef, const Fr *w,
-                       Fr *out) {
-        hipLaunchKernelGGL((k_shplonk_combine<FrP>), dim3((unsigned)((maxlen + 255) / 256)), dim3(256), 0, stream, polys, off_len, k, maxlen,
-                           coef, w, out);
-        HIP_TRY(hipGetLastError());
-        return GMSM_OK;
     }
 };
 

@@ -1,6 +1,7 @@
 // Stand-alone host check of FflonkField (gmsm_fflonk.h), no GPU: the divisors, the root of one, the extended sets, both sets
-// of claimed values from host-computed chain remainders, the index tables and the refusals, printed for
-// tests/test_fflonk_host.py to compare with tests/fflonk_model.py. Built there with AddressSanitizer on the host side.
+// of claimed values from host-computed chain remainders, the index tables and the refusals, then the same plan in shplonk's
+// singleton form, printed for tests/test_fflonk_host.py to compare with tests/fflonk_model.py and tests/shplonk_model.py.
+// Built there with AddressSanitizer on the host side.
 #include <cstdio>
 #include "gmsm_fflonk.h"
 using namespace gmsm;
@@ -10,6 +11,31 @@ template <class FrP> static void put(const char *tag, const Fp<FrP> &x) {
     Fp<FrP> t = fp_from_mont(x);
     printf("%s 0x", tag);
     for (int i = FrP::N - 1; i >= 0; --i) printf("%08x", t.l[i]);
+    printf("\n");
+}
+// the chains' remainders by plain synthetic division on the host
+template <class FrP> static std::vector<Fp<FrP>> remainders(const typename FflonkField<FrP>::Plan &p, const std::vector<Fp<FrP>> &flat, const size_t *lens) {
+    using Fr = Fp<FrP>;
+    std::vector<Fr> rem(p.nrem, Fr::zero());
+    size_t off = 0, r = 0;
+    for (size_t i = 0, at = 0; i < p.k; at += p.m[i], ++i)
+        for (size_t j = 0; j < p.count[i]; off += lens[p.first[i] + j], r += p.m[i], ++j) {
+            std::vector<Fr> q(flat.begin() + off, flat.begin() + off + lens[p.first[i] + j]);
+            for (size_t c = 0; c < p.m[i] && !q.empty(); ++c) {
+                Fr y = Fr::zero();
+                std::vector<Fr> ys(q.size());
+                for (size_t e = q.size(); e-- > 0;) y = fp_add(q[e], fp_mul(p.a[at + c], y)), ys[e] = y;
+                rem[r + c] = ys[0];
+                q.assign(ys.begin() + 1, ys.end());
+            }
+        }
+    return rem;
+}
+template <class FrP> static void put_tables(const char *tag, const typename FflonkField<FrP>::Plan &p, const size_t *lens) {
+    std::vector<uint64_t> tbl(p.table_words());
+    FflonkField<FrP>::tables(p, lens, tbl.data());
+    printf("%s", tag);
+    for (uint64_t v : tbl) printf(" %llu", (unsigned long long)v);
     printf("\n");
 }
 template <class FrP> static void run(const char *name) {
@@ -27,29 +53,12 @@ template <class FrP> static void run(const char *name) {
     int rc = FF::plan("check", lens, pack_sizes, 2, (const uint64_t *)pts, npoints, true, 1000, &p);
     printf("plan %d maxfold %zu wlen %zu nrem %zu next %zu\n", rc, p.maxfold, p.wlen, p.nrem, p.next);
     for (size_t i = 0; i < p.ext.size(); ++i) put<FrP>("ext", p.ext[i]);
-    // the chains' remainders by plain synthetic division on the host
-    std::vector<Fr> rem(p.nrem, Fr::zero());
-    size_t off = 0, r = 0;
-    for (size_t i = 0, at = 0; i < p.k; at += p.m[i], ++i)
-        for (size_t j = 0; j < p.count[i]; off += lens[p.first[i] + j], r += p.m[i], ++j) {
-            std::vector<Fr> q(flat.begin() + off, flat.begin() + off + lens[p.first[i] + j]);
-            for (size_t c = 0; c < p.m[i] && !q.empty(); ++c) {
-                Fr y = Fr::zero();
-                std::vector<Fr> ys(q.size());
-                for (size_t e = q.size(); e-- > 0;) y = fp_add(q[e], fp_mul(p.a[at + c], y)), ys[e] = y;
-                rem[r + c] = ys[0];
-                q.assign(ys.begin() + 1, ys.end());
-            }
-        }
+    std::vector<Fr> rem = remainders<FrP>(p, flat, lens);
     std::vector<Fr> claimed(p.next), folded(p.next);
     FF::claimed_values(p, rem.data(), claimed.data(), folded.data());
     for (auto &x : claimed) put<FrP>("claimed", x);
     for (auto &x : folded) put<FrP>("folded", x);
-    std::vector<uint64_t> tbl(2 * p.npolys + 3 * p.k);
-    FF::tables(p, lens, tbl.data());
-    printf("tables");
-    for (uint64_t v : tbl) printf(" %llu", (unsigned long long)v);
-    printf("\n");
+    put_tables<FrP>("tables", p, lens);
     // refusals
     Fr bad[2] = {small<FrP>(1), fp_neg(small<FrP>(1))};
     size_t l2[2] = {3, 3}, ps[1] = {2}, np2[1] = {2};
@@ -58,6 +67,25 @@ template <class FrP> static void run(const char *name) {
     printf("zero_t2 %d\n", FF::plan("check", l2, ps, 1, (const uint64_t *)&zero, np1, true, 1000, &p));
     printf("size_short %d\n", FF::plan("check", l2, ps, 1, (const uint64_t *)pts, np2, true, 2 * 3 + 4 - 2, &p));
     printf("size_exact %d\n", FF::plan("check", l2, ps, 1, (const uint64_t *)pts, np2, true, 2 * 3 + 4 - 1, &p));
+    // singleton form (pack_sizes == null, shplonk): [1,2,3] at {3,5}, [4,5] at {2}, [7] at {2,9} - a point shared by two sets,
+    // and a chain that runs out of coefficients
+    size_t slens[3] = {3, 2, 1}, snp[3] = {2, 1, 2};
+    std::vector<Fr> sflat(flat.begin(), flat.begin() + 6);
+    Fr spts[5] = {small<FrP>(3), small<FrP>(5), small<FrP>(2), small<FrP>(2), small<FrP>(9)};
+    rc = FF::plan("check", slens, nullptr, 3, (const uint64_t *)spts, snp, true, 1000, &p);
+    printf("s_plan %d maxfold %zu wlen %zu nrem %zu\n", rc, p.maxfold, p.wlen, p.nrem);
+    put_tables<FrP>("s_tables", p, slens);
+    rem = remainders<FrP>(p, sflat, slens);
+    std::vector<Fr> sclaimed(p.np);
+    FF::claimed_values(p, rem.data(), sclaimed.data(), nullptr);
+    for (auto &x : sclaimed) put<FrP>("s_claimed", x);
+    // refusals: a point twice in one set; one point in two sets; a key one base short of max_size + sum m_i - 1, then exact
+    Fr twice[2] = {small<FrP>(3), small<FrP>(3)};
+    size_t one[1] = {3}, two[1] = {2}, l2s[2] = {3, 3}, np11[2] = {1, 1};
+    printf("s_equal %d\n", FF::plan("check", one, nullptr, 1, (const uint64_t *)twice, two, true, 1000, &p));
+    printf("s_shared %d\n", FF::plan("check", l2s, nullptr, 2, (const uint64_t *)twice, np11, true, 1000, &p));
+    printf("s_size_short %d\n", FF::plan("check", slens, nullptr, 3, (const uint64_t *)spts, snp, true, 3 + 5 - 2, &p));
+    printf("s_size_exact %d\n", FF::plan("check", slens, nullptr, 3, (const uint64_t *)spts, snp, true, 3 + 5 - 1, &p));
 }
 int main() {
     run<bn254_fr_params>("bn254");
