@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "gmsm_points_from_compressed", "gmsm_points_compress", "gmsm_bases_register_compressed",
     "gmsm_bases_register_dump", "gmsm_fft_domain_new", "gmsm_fft_domain_release", "gmsm_fft_domain_info", "gmsm_fft",
     "gmsm_fft_bit_reverse", "gmsm_poly_eval", "gmsm_poly_div_x_minus_a", "gmsm_kzg_open", "gmsm_kzg_open_folded",
-    "gmsm_to_lagrange_g1", "gmsm_bases_to_lagrange", "gmsm_shplonk_open_w", "gmsm_shplonk_open_wprime",
+    "gmsm_to_lagrange_g1", "gmsm_bases_to_lagrange", "gmsm_batch_scale", "gmsm_update_monomials", "gmsm_linear_combinations", "gmsm_shplonk_open_w", "gmsm_shplonk_open_wprime",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
     "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
@@ -179,6 +179,12 @@ def load():
     L.gmsm_to_lagrange_g1.argtypes = [ctypes.c_int, u64p, vp, sz, vp, u64p, vp]
     L.gmsm_bases_to_lagrange.restype = ctypes.c_int
     L.gmsm_bases_to_lagrange.argtypes = [ctypes.c_uint64, sz, ctypes.POINTER(ctypes.c_uint64)]
+    L.gmsm_batch_scale.restype = ctypes.c_int
+    L.gmsm_batch_scale.argtypes = [ctypes.c_int, u64p, vp, sz, u64p, vp, sz, vp, u64p, vp]
+    L.gmsm_update_monomials.restype = ctypes.c_int
+    L.gmsm_update_monomials.argtypes = [ctypes.c_int, u64p, vp, sz, u64p, vp, u64p, vp]
+    L.gmsm_linear_combinations.restype = ctypes.c_int
+    L.gmsm_linear_combinations.argtypes = [ctypes.c_int, u64p, vp, sz, szp, sz, u64p, vp, u64p, u64p]
     L.gmsm_shplonk_open_w.restype = ctypes.c_int
     L.gmsm_shplonk_open_w.argtypes = [ctypes.c_uint64, u64p, vp, szp, sz, u64p, szp, u64p, vp, u64p, u64p, vp, u64p]
     L.gmsm_shplonk_open_wprime.restype = ctypes.c_int

@@ -181,7 +181,7 @@ struct Workspace {
     DeviceBuffer h2d_points, h2d_scalars;  // staging of the host-pointer entries
     DeviceBuffer raw_bytes, flagword;      // point ingest: wire-format bytes, first-offender word
     DeviceBuffer poly;                     // KZG opening (gmsm_poly.h): folded polynomial, quotient, lane and tile carries
-    DeviceBuffer lagrange;                 // ToLagrangeG1 (gmsm_group_fft.h): records, GLV walk table, twiddles
+    DeviceBuffer lagrange;                 // ToLagrangeG1 (gmsm_group_fft.h): records, GLV walk table, twiddles; the batch of gmsm_scale.h: its walk table
     bool busy = false;  // leased to a call (Context::acquire / release)
     bool ticket = false;  // ... by gmsm_multiexp_bases_submit: only gmsm_multiexp_collect ends that lease
     // state of a submitted, not yet collected call
@@ -728,6 +728,13 @@ struct GroupVTable {
                        const uint64_t *points, const size_t *npoints, const uint64_t *folded_claimed, const uint64_t *gamma,
                        const uint64_t *w, const void *d_w, const uint64_t *z, hipStream_t stream, uint64_t *out_jac,
                        const ResidentBases *resident);
+    // mpcsetup updates (gmsm_scale.h): out[i] = s_i points[i] with s_i = scalars[i] (n_scalars == n), scalars[0] (n_scalars == 1)
+    // or r^i (`r` given: no scalars); points, scalars and the output each on the host or on the device, n > 0
+    int (*batch_scale)(Context &ctx, const uint64_t *points, const void *d_points, size_t n, const uint64_t *scalars, const void *d_scalars,
+                       size_t n_scalars, const uint64_t *r, hipStream_t stream, uint64_t *out_affine, void *d_out_affine);
+    // linearCombinationsG1/G2: the two sums over powers of r with zeros at the segment ends (checked by the caller), Jacobian
+    int (*linear_combinations)(Context &ctx, const uint64_t *points, const void *d_points, size_t n, const size_t *ends, size_t n_ends,
+                               const uint64_t *r, hipStream_t stream, uint64_t *out_truncated_jac, uint64_t *out_shifted_jac);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

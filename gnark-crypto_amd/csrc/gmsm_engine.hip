@@ -1657,6 +1657,61 @@ GMSM_EXPORT int gmsm_bases_to_lagrange(uint64_t handle, size_t n, uint64_t *out_
     return GMSM_OK;
 }
 
+// ------------------------------------------------------------------ mpcsetup updates (gmsm_scale.h)
+// the pointer pairs of the two batch entries, then the call through the vtable
+static int scale_call(const char *E, const GroupVTable *vt, const uint64_t *points, const void *d_points, size_t n, const uint64_t *scalars,
+                      const void *d_scalars, size_t n_scalars, const uint64_t *r, void *hip_stream, uint64_t *out_affine, void *d_out_affine) {
+    if ((points == nullptr) == (d_points == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of points (host) / d_points (device)");
+    if (!r && (scalars == nullptr) == (d_scalars == nullptr))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of scalars (host) / d_scalars (device)");
+    if ((out_affine == nullptr) == (d_out_affine == nullptr))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_affine (host) / d_out_affine (device)");
+    Context *ctx;
+    int rc = get_context_of_pointer(d_points ? d_points : d_out_affine ? d_out_affine : d_scalars, &ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_points", d_points, ctx->device)) || (rc = check_device_vector(E, "d_scalars", d_scalars, ctx->device)) ||
+        (rc = check_device_vector(E, "d_out_affine", d_out_affine, ctx->device)))
+        return rc;
+    return vt->batch_scale(*ctx, points, d_points, n, scalars, d_scalars, n_scalars, r, (hipStream_t)hip_stream, out_affine, d_out_affine);
+}
+
+GMSM_EXPORT int gmsm_batch_scale(int group, const uint64_t *points, const void *d_points, size_t n, const uint64_t *scalars,
+                                 const void *d_scalars, size_t n_scalars, void *hip_stream, uint64_t *out_affine, void *d_out_affine) {
+    VT_OR_FAIL(group);
+    if (n_scalars != n && n_scalars != 1) return fail(GMSM_ERR_LEN, "gmsm_batch_scale: n_scalars must be n (one scalar per point) or 1 (one for all)");
+    if (n == 0) return GMSM_OK;
+    return scale_call("gmsm_batch_scale", vt, points, d_points, n, scalars, d_scalars, n_scalars, nullptr, hip_stream, out_affine, d_out_affine);
+}
+
+GMSM_EXPORT int gmsm_update_monomials(int group, const uint64_t *points, const void *d_points, size_t n, const uint64_t *r, void *hip_stream,
+                                      uint64_t *out_affine, void *d_out_affine) {
+    VT_OR_FAIL(group);
+    if (n < 2) return fail(GMSM_ERR_ARG, "gmsm_update_monomials: needs at least 2 points (UpdateMonomialsG1 starts at A[1])");
+    if (!r) return fail(GMSM_ERR_ARG, "gmsm_update_monomials: r is null");
+    return scale_call("gmsm_update_monomials", vt, points, d_points, n, nullptr, nullptr, 0, r, hip_stream, out_affine, d_out_affine);
+}
+
+GMSM_EXPORT int gmsm_linear_combinations(int group, const uint64_t *points, const void *d_points, size_t n, const size_t *ends, size_t n_ends,
+                                         const uint64_t *r, void *hip_stream, uint64_t *out_truncated_jac, uint64_t *out_shifted_jac) {
+    VT_OR_FAIL(group);
+    const char *E = "gmsm_linear_combinations";
+    if ((points == nullptr) == (d_points == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of points (host) / d_points (device)");
+    if (!ends || !n_ends || !r || !out_truncated_jac || !out_shifted_jac)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": ends, r, out_truncated_jac and out_shifted_jac must not be null, n_ends not 0");
+    for (size_t j = 0, prev = 0; j < n_ends; prev = ends[j], ++j) {
+        if (ends[j] <= prev) return fail(GMSM_ERR_ARG, std::string(E) + ": ends must be strictly increasing");
+        if (ends[j] - prev < 2) return fail(GMSM_ERR_ARG, "each slice must be of length at least 2");
+    }
+    if (ends[n_ends - 1] != n) return fail(GMSM_ERR_ARG, "lengths mismatch");
+    Context *ctx;
+    int rc = get_context_of_pointer(d_points, &ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = check_device_vector(E, "d_points", d_points, ctx->device))) return rc;
+    return vt->linear_combinations(*ctx, points, d_points, n, ends, n_ends, r, (hipStream_t)hip_stream, out_truncated_jac, out_shifted_jac);
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {

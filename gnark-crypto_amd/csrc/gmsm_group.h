@@ -23,6 +23,7 @@
 #include "gmsm_shplonk.h"
 #include "gmsm_fflonk.h"
 #include "gmsm_group_fft.h"
+#include "gmsm_scale.h"
 
 namespace gmsm {
 
@@ -831,7 +832,7 @@ struct Group : GroupHost<F_, FrP_> {
     static constexpr bool LAGRANGE_GLV = GMSM_LAGRANGE_GLV != 0;
     static int to_lagrange(Workspace &ws, const void *d_in, bool packed, unsigned log2n, void *d_out) {
         static_assert(std::is_same<U, FpU<typename LzTraits<U>::Params>>::value, "ToLagrangeG1: coordinates in Fp");
-        using Tw = LagTw<FrP, LAGRANGE_GLV>;
+        using Tw = WalkScalar<FrP, LAGRANGE_GLV>;
         using Fld = FftField<FrP>;
         using Fr = Fp<FrP>;
         constexpr size_t REC = sizeof(XYZZL<U>);
@@ -868,6 +869,59 @@ struct Group : GroupHost<F_, FrP_> {
         }
         HIP_TRY(hipGetLastError());
         return normalize_records(ws, n, d_out);
+    }
+
+    // Variable-base batch (gmsm_scale.h): d_out[i] = s_i d_in[i] for n Go-layout affine points on the device, s_i =
+    // d_scalars[i] (Montgomery fr.Elements), d_scalars[0] (`uniform`) or r^i (`r` given, d_scalars unused). d_out may be d_in:
+    // every point is a record in ws.buckets before the normalisation writes. Scratch: ws.buckets (the records), ws.lagrange
+    // (the walk's table for one chunk of lanes), ws.partials (the normalisation's prefix products).
+#ifndef GMSM_SCALE_GLV
+#define GMSM_SCALE_GLV 1
+#endif
+    static constexpr bool SCALE_GLV = GMSM_SCALE_GLV != 0;
+    static int batch_scale(Workspace &ws, const void *d_in, size_t n, const void *d_scalars, bool uniform, const Fp<FrP> *r, void *d_out) {
+        if (n == 0) return GMSM_OK;
+        using Fr = Fp<FrP>;
+        constexpr size_t REC = sizeof(XYZZL<U>);
+        int rc;
+        if ((rc = ws.buckets.ensure(n * REC))) return rc;
+        if (SCALE_GLV && (rc = ws.lagrange.ensure(3 * std::min(n, SCALE_CHUNK) * REC))) return rc;
+        for (size_t first = 0; first < n; first += SCALE_CHUNK) {
+            const size_t count = std::min(SCALE_CHUNK, n - first);
+            const dim3 grid((unsigned)((count + 255) / 256)), block(256);
+            if (r)
+                hipLaunchKernelGGL((k_scale_powers<U, Consts, FrP, SCALE_GLV, INLINE_OPS>), grid, block, 0, ws.stream, d_in, first, count,
+                                   FftField<FrP>::powers_of(*r), ws.buckets.ptr, ws.lagrange.ptr);
+            else if (uniform)
+                hipLaunchKernelGGL((k_batch_scale<U, Consts, FrP, SCALE_GLV, INLINE_OPS, true>), grid, block, 0, ws.stream, d_in, first,
+                                   count, (const Fr *)d_scalars, ws.buckets.ptr, ws.lagrange.ptr);
+            else
+                hipLaunchKernelGGL((k_batch_scale<U, Consts, FrP, SCALE_GLV, INLINE_OPS, false>), grid, block, 0, ws.stream, d_in, first,
+                                   count, (const Fr *)d_scalars, ws.buckets.ptr, ws.lagrange.ptr);
+        }
+        HIP_TRY(hipGetLastError());
+        return normalize_records(ws, n, d_out);
+    }
+
+    // linearCombinationsG1/G2 (mpcsetup.go:396-447): with powers[i] = r^i and zeros at ends[j] - 1, truncated = MultiExp(A,
+    // powers) and shifted = MultiExp(A[1:], powers[:n - 1]) through the device path. n >= 2 and the ends are checked by the
+    // caller; `ends` is host memory. Scratch beside the MultiExp's own: ws.poly (the powers, the ends).
+    static int linear_combinations(Context &ctx, Workspace &ws, const void *d_points, size_t n, const size_t *ends, size_t n_ends,
+                                   const Fp<FrP> &r, J *truncated, J *shifted) {
+        using Fr = Fp<FrP>;
+        static_assert(sizeof(size_t) == sizeof(uint64_t), "ends are copied as 64-bit words");
+        int rc;
+        if ((rc = ws.poly.ensure(n * sizeof(Fr) + n_ends * sizeof(uint64_t)))) return rc;
+        Fr *pow = (Fr *)ws.poly.ptr;
+        uint64_t *d_ends = (uint64_t *)(pow + n);
+        HIP_TRY(hipMemcpyAsync(d_ends, ends, n_ends * sizeof(uint64_t), hipMemcpyHostToDevice, ws.stream));
+        hipLaunchKernelGGL((k_fft_pow_table<FrP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ws.stream, FftField<FrP>::powers_of(r),
+                           Fr::one(), n, pow, 0u);
+        hipLaunchKernelGGL((k_zero_at<FrP>), dim3((unsigned)((n_ends + 255) / 256)), dim3(256), 0, ws.stream, pow, (const uint64_t *)d_ends,
+                           n_ends);
+        HIP_TRY(hipGetLastError());
+        if ((rc = multiexp_device(ctx, ws, d_points, pow, n, ws.stream, truncated, nullptr))) return rc;
+        return multiexp_device(ctx, ws, (const char *)d_points + AFF_BYTES, pow, n - 1, ws.stream, shifted, nullptr);
     }
 
     // Rewrites n Go-layout bases (device memory) into the lazy domain once; the result serves any number of MultiExp

@@ -27,13 +27,14 @@
 //   mulGLV walks the same pair two bits at a time, ecc/bn254/g1.go:529-600). The three entries of a lane live in a
 //   workspace table in HBM (one record-sized slot per lane and entry, read back by the lane that wrote it): a table in
 //   registers does not fit BW6-761's 108-word records. GMSM_LAGRANGE_GLV=0: a plain binary walk over the full scalar.
+//   The walk itself is walk_mul (gmsm_walk.h), shared with the variable-base batch of gmsm_scale.h.
 // 1/n is folded into the first stage: b' takes w^-i / n, a' one extra product by 1/n - n/2 scalar multiplications
 // instead of n. n = 1 has no stage: the input, normalised.
 // Precondition (as the reference's ScalarMultiplication = mulGLV): every input lies in the r-torsion.
 #pragma once
 #include "gmsm_fixedbase.h"
 #include "gmsm_fft.h"
-#include "gmsm_glv.h"
+#include "gmsm_walk.h"
 
 #ifndef GMSM_LAGRANGE_GLV
 #define GMSM_LAGRANGE_GLV 1
@@ -41,22 +42,10 @@
 
 namespace gmsm {
 
-// One twiddle as the stage kernels read it: the GLV halves (magnitudes, bit 0 / 1 of `neg` their signs) or the scalar
-// itself, both in regular (not Montgomery) form.
-template <class FrP, bool GLV>
-struct LagTw {
-    uint32_t k1[FrP::GLV_HL], k2[FrP::GLV_HL];
-    uint32_t neg;
-};
-template <class FrP>
-struct LagTw<FrP, false> {
-    uint32_t s[FrP::N];
-};
-
 // out[e], e < 2 half + 1: w^-e (e < half), w^-(e - half) / n (e < 2 half), 1/n (e = 2 half); pw = powers of w^-1
 template <class FrP, bool GLV>
 __global__ void __launch_bounds__(256) k_group_fft_twiddles(FftPowers<FrP> pw, Fp<FrP> ninv, size_t half,
-                                                            LagTw<FrP, GLV> *__restrict__ out) {
+                                                            WalkScalar<FrP, GLV> *__restrict__ out) {
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e > 2 * half) return;
     const size_t x = e < half ? e : e < 2 * half ? e - half : 0;
@@ -64,17 +53,7 @@ __global__ void __launch_bounds__(256) k_group_fft_twiddles(FftPowers<FrP> pw, F
 #pragma nounroll
     for (int b = 0; b < 40; ++b)
         if ((x >> b) & 1) acc = fp_mul(acc, pw.p[b]);
-    acc = fp_from_mont(acc);
-    LagTw<FrP, GLV> t;
-    if constexpr (GLV) {
-        bool n1, n2;
-        glv_split<FrP>(acc.l, t.k1, n1, t.k2, n2);
-        t.neg = (n1 ? 1u : 0u) | (n2 ? 2u : 0u);
-    } else {
-#pragma unroll
-        for (int k = 0; k < FrP::N; ++k) t.s[k] = acc.l[k];
-    }
-    out[e] = t;
+    out[e] = walk_scalar<FrP, GLV>(acc);
 }
 
 // points -> lazy XYZZ records (ZZ = ZZZ = 1; infinity: zero ZZ limbs)
@@ -100,77 +79,6 @@ __global__ void __launch_bounds__(256) k_group_fft_load(const void *__restrict__
     lazy_store<U>(recs, i, r, inf);
 }
 
-// -P of a stored record: 8q - y carry-passed, back into [0, 4q)
-template <class P>
-__device__ __forceinline__ void lag_negate_y(XYZZU<P> &p) {
-    p.y = fpu_negc<P, 8>(p.y);
-    fpu_to_class_r(p.y);
-}
-
-template <int L>
-__device__ __forceinline__ void lag_shl1(uint32_t (&k)[L]) {
-#pragma unroll
-    for (int i = L - 1; i > 0; --i) k[i] = (k[i] << 1) | (k[i - 1] >> 31);
-    k[0] <<= 1;
-}
-
-// e = [tw] e. `tab` holds 3 record slots per lane (slot, slot + stride, slot + 2 stride), used by the GLV walk only.
-template <class P, class C, class FrP, bool GLV, bool INL>
-__device__ __forceinline__ void lag_twiddle_mul(UnsatElem<FpU<P>> &e, const LagTw<FrP, GLV> &tw, void *__restrict__ tab, size_t slot,
-                                                size_t stride) {
-    using U = FpU<P>;
-    if (e.inf) return;
-    XYZZL<U> acc;
-    bool inf = true;
-    if constexpr (GLV) {
-        constexpr int HL = FrP::GLV_HL;
-        XYZZL<U> p1 = e.v, p2 = e.v;
-        p2.x = fmul<INL>(e.v.x, glv_w<U, C, INL>());  // phi
-        if (tw.neg & 1u) lag_negate_y(p1);
-        if (tw.neg & 2u) lag_negate_y(p2);
-        lazy_store<U>(tab, slot, p1, false);
-        lazy_store<U>(tab, slot + stride, p2, false);
-        bool inf3 = false;
-        add_u<P, INL>(p1, inf3, p2, false);
-        lazy_store<U>(tab, slot + 2 * stride, p1, inf3);
-        uint32_t k1[HL], k2[HL];
-#pragma unroll
-        for (int k = 0; k < HL; ++k) k1[k] = tw.k1[k], k2[k] = tw.k2[k];
-        constexpr int SKIP = 32 * HL - FrP::GLV_BITS;  // bits above GLV_BITS are zero
-#pragma unroll
-        for (int b = 0; b < SKIP; ++b) lag_shl1(k1), lag_shl1(k2);
-#pragma nounroll
-        for (int b = 0; b < FrP::GLV_BITS; ++b) {
-            if (!inf) acc = double_u<P, INL>(acc);
-            const uint32_t sel = (k1[HL - 1] >> 31) | ((k2[HL - 1] >> 30) & 2u);
-            lag_shl1(k1);
-            lag_shl1(k2);
-            if (sel) {
-                const UnsatElem<U> t = unsat_load<U>(tab, slot + (sel - 1u) * stride);
-                add_u<P, INL>(acc, inf, t.v, t.inf);
-            }
-        }
-    } else {
-        (void)tab, (void)slot, (void)stride;
-        constexpr int N = FrP::N;
-        uint32_t s[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) s[k] = tw.s[k];
-        constexpr int SKIP = 32 * N - (int)FrP::BITS;
-#pragma unroll
-        for (int b = 0; b < SKIP; ++b) lag_shl1(s);
-#pragma nounroll
-        for (int b = 0; b < (int)FrP::BITS; ++b) {
-            if (!inf) acc = double_u<P, INL>(acc);
-            const bool bit = (s[N - 1] >> 31) != 0u;
-            lag_shl1(s);
-            if (bit) add_u<P, INL>(acc, inf, e.v, false);
-        }
-    }
-    e.v = acc;
-    e.inf = inf;
-}
-
 __device__ __forceinline__ size_t lag_bitrev(size_t i, unsigned log2n) {
     return log2n ? (size_t)(__brevll((unsigned long long)i) >> (64 - log2n)) : 0;
 }
@@ -183,7 +91,7 @@ __device__ __forceinline__ size_t lag_bitrev(size_t i, unsigned log2n) {
 // is. The last stage (s = log2n - 1) writes to bit-reversed positions (bitReverse), out of place.
 template <class P, class C, class FrP, bool GLV, bool INL>
 __global__ void __launch_bounds__(256) k_group_fft_stage(const void *src, void *dst, unsigned log2n, unsigned s,
-                                                         const LagTw<FrP, GLV> *__restrict__ tw, void *__restrict__ tab) {
+                                                         const WalkScalar<FrP, GLV> *__restrict__ tw, void *__restrict__ tab) {
     using U = FpU<P>;
     const size_t half = (size_t)1 << (log2n - 1);
     const bool first = s == 0;
@@ -205,13 +113,13 @@ __global__ void __launch_bounds__(256) k_group_fft_stage(const void *src, void *
     UnsatElem<U> a = unsat_load<U>(src, pa), b = unsat_load<U>(src, pb);
     UnsatElem<U> d = a;
     add_u<P, INL>(a.v, a.inf, b.v, b.inf);  // a + b
-    if (!b.inf) lag_negate_y(b.v);
+    if (!b.inf) walk_negate_y(b.v);
     add_u<P, INL>(d.v, d.inf, b.v, b.inf);  // a - b
     const bool last = s + 1 == log2n;
     if (!first) lazy_store<U>(dst, last ? lag_bitrev(pa, log2n) : pa, a.v, a.inf);  // before the walk: frees a's registers
     UnsatElem<U> x = sum_job ? a : d;
     const size_t twi = sum_job ? 2 * half : first ? half + i : i << s;
-    if (first || twi != 0) lag_twiddle_mul<P, C, FrP, GLV, INL>(x, tw[twi], tab, t, jobs);  // else: twiddle 1
+    if (first || twi != 0) walk_mul<U, C, FrP, GLV, INL>(x, tw[twi], tab, t, jobs);  // else: twiddle 1
     const size_t px = sum_job ? pa : pb;
     lazy_store<U>(dst, last ? lag_bitrev(px, log2n) : px, x.v, x.inf);
 }

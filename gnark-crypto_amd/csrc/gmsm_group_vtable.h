@@ -453,13 +453,66 @@ struct VTableOf {
         if constexpr (IS_G1) return &to_lagrange;
         else return nullptr;
     }
+    // ---- mpcsetup updates (gmsm_scale.h)
+    static int batch_scale(Context &ctx, const uint64_t *points, const void *d_points, size_t n, const uint64_t *scalars, const void *d_scalars,
+                           size_t n_scalars, const uint64_t *r, hipStream_t caller, uint64_t *out_affine, void *d_out_affine) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const size_t bytes = n * G::AFF_BYTES;
+        int rc;
+        const void *src = d_points, *dsc = d_scalars;
+        if (points) {
+            if ((rc = ws.h2d_points.ensure(bytes))) return rc;
+            HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, points, bytes, hipMemcpyHostToDevice, ws.stream));
+            src = ws.h2d_points.ptr;
+        }
+        if (scalars) {
+            if ((rc = ws.h2d_scalars.ensure(n_scalars * sizeof(Fr)))) return rc;
+            HIP_TRY(hipMemcpyAsync(ws.h2d_scalars.ptr, scalars, n_scalars * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+            dsc = ws.h2d_scalars.ptr;
+        }
+        if ((d_points || d_scalars || d_out_affine) && (rc = order_after(ws, caller))) return rc;  // the caller's stream owns those vectors
+        void *dst = d_out_affine;
+        if (!dst) {  // host output: staged in h2d_points (the kernels have read any host input by the time it is written)
+            if ((rc = ws.h2d_points.ensure(bytes))) return rc;
+            dst = ws.h2d_points.ptr;
+        }
+        Fr rr;
+        if (r) memcpy(&rr, r, sizeof rr);
+        if ((rc = G::batch_scale(ws, src, n, dsc, n_scalars == 1, r ? &rr : nullptr, dst))) return rc;
+        if (out_affine) HIP_TRY(hipMemcpyAsync(out_affine, dst, bytes, hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    static int linear_combinations(Context &ctx, const uint64_t *points, const void *d_points, size_t n, const size_t *ends, size_t n_ends,
+                                   const uint64_t *r, hipStream_t caller, uint64_t *out_truncated_jac, uint64_t *out_shifted_jac) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        int rc;
+        const void *src = d_points;
+        if (points) {
+            if ((rc = ws.h2d_points.ensure(n * G::AFF_BYTES))) return rc;
+            HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, points, n * G::AFF_BYTES, hipMemcpyHostToDevice, ws.stream));
+            src = ws.h2d_points.ptr;
+        } else if ((rc = order_after(ws, caller))) {
+            return rc;
+        }
+        Fr rr;
+        memcpy(&rr, r, sizeof rr);
+        typename G::J t, s;
+        if ((rc = G::linear_combinations(ctx, ws, src, n, ends, n_ends, rr, &t, &s))) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        memcpy(out_truncated_jac, &t, sizeof t);
+        memcpy(out_shifted_jac, &s, sizeof s);
+        return GMSM_OK;
+    }
     static const GroupVTable *get() {
         static const GroupVTable vt = {G::FR_BITS,      G::AFF_BYTES,   G::SCALAR_BYTES, sizeof(typename G::J),
                                        sizeof(typename G::Ext), &multiexp_host, &multiexp_device, &window_sums,
                                        &fold,           &jac_to_affine, &debug_decompose, &debug_field_op,
                                        &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info,
                                        &poly_eval, &poly_div, &kzg_open, lagrange_entry(),
-                                       &fflonk_next_divisor, &open_check, &fflonk_fold, open_w_entry(), open_wprime_entry(),
+                                       &fflonk_next_divisor, &open_check, &fflonk_fold, open_w_entry(), open_wprime_entry(), &batch_scale, &linear_combinations,
                                        (unsigned)G::FrP::MAX_ORDER};
         return &vt;
     }

@@ -387,6 +387,39 @@ int gmsm_to_lagrange_g1(int group, const uint64_t *coeffs, const void *d_coeffs,
                         uint64_t *out_affine, void *d_out_affine);
 int gmsm_bases_to_lagrange(uint64_t handle, size_t n, uint64_t *out_handle);
 
+/* ---- mpcsetup updates (ecc/<curve>/mpcsetup, ecc/<curve>/kzg/mpcsetup.go): variable-base batch scalar multiplication on
+ *      the device, one lane per point (gmsm_scale.h), for all six groups. Results are canonical affine limbs (infinity =
+ *      (0, 0)), bit-identical to the reference's ScalarMultiplication followed by FromJacobian.
+ *   Precondition (as the reference's ScalarMultiplication, mulGLV): every input point lies in the r-torsion; the walk uses
+ *      the GLV endomorphism. Verify subgroup-checks first (gmsm_points_validate).
+ *   Conventions of the three entries: n points in from exactly one of points (host) / d_points (device, 16-byte aligned,
+ *      produced on hip_stream); inputs are not modified unless the output aliases them; the call returns when the result
+ *      is complete; scratch comes from the call's workspace. An unknown group id is GMSM_ERR_ARG.
+ *   gmsm_batch_scale: out[i] = scalars[i] * points[i] (n_scalars == n; Montgomery fr.Elements, from exactly one of scalars
+ *      / d_scalars) or scalars[0] * points[i] (n_scalars == 1: the slice cases of mpcsetup.UpdateValues). Any other
+ *      n_scalars: GMSM_ERR_LEN. Out to exactly one of out_affine / d_out_affine; the output may alias the input points.
+ *      n == 0 is GMSM_OK and touches nothing. An input at infinity stays; scalar 0 gives infinity.
+ *   gmsm_update_monomials: UpdateMonomialsG1, out[0] = points[0], out[i] = r^i * points[i], r one Montgomery fr.Element on
+ *      the host; r^i is made on the device, no scalar vector exists. n < 2: GMSM_ERR_ARG (the reference indexes A[1]). The
+ *      group id decides the point type: all six work (the reference's UpdateMonomialsG2 takes []G1Affine as generated).
+ *   gmsm_linear_combinations: linearCombinationsG1/G2 (mpcsetup.go:396-447, :489-540). With `ends` the running ends of the
+ *      segments of `points` (host, strictly increasing, ends[n_ends - 1] == n) and powers[i] = r^i over the flat index,
+ *        truncated = sum r^i points[i]      over every i that is not the last of its segment,
+ *        shifted   = sum r^i points[i + 1]  over the same i,
+ *      as two MultiExps over device-made powers with zeros at ends[j] - 1; Jacobian {X,Y,Z} to host memory. The reference
+ *      reaches `shifted` by way of r^-1 * truncated, the same group element for points in the r-torsion (the precondition
+ *      above). GMSM_ERR_ARG before any device work: ends not strictly increasing, a segment shorter than 2 ("each slice
+ *      must be of length at least 2"), ends[n_ends - 1] != n ("lengths mismatch"), a null required pointer. (linearCombinationG1
+ *      /G2 with caller-supplied scalars is gmsm_multiexp.) ---- */
+int gmsm_batch_scale(int group, const uint64_t *points, const void *d_points, size_t n,
+                     const uint64_t *scalars, const void *d_scalars, size_t n_scalars,
+                     void *hip_stream, uint64_t *out_affine, void *d_out_affine);
+int gmsm_update_monomials(int group, const uint64_t *points, const void *d_points, size_t n, const uint64_t *r,
+                          void *hip_stream, uint64_t *out_affine, void *d_out_affine);
+int gmsm_linear_combinations(int group, const uint64_t *points, const void *d_points, size_t n,
+                             const size_t *ends, size_t n_ends, const uint64_t *r, void *hip_stream,
+                             uint64_t *out_truncated_jac, uint64_t *out_shifted_jac);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals
