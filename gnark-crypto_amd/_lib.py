@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "gmsm_fft_bit_reverse", "gmsm_poly_eval", "gmsm_poly_div_x_minus_a", "gmsm_kzg_open", "gmsm_kzg_open_folded",
     "gmsm_to_lagrange_g1", "gmsm_bases_to_lagrange", "gmsm_batch_scale", "gmsm_update_monomials", "gmsm_linear_combinations", "gmsm_shplonk_open_w", "gmsm_shplonk_open_wprime",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
-    "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
+    "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
     "gmsm_device_count", "gmsm_set_device", "gmsm_last_error",
     "gmsm_version",
@@ -91,6 +91,8 @@ def load():
     L.gmsm_debug_table_runs.argtypes = []
     L.gmsm_debug_small_runs.restype = ctypes.c_ulong
     L.gmsm_debug_small_runs.argtypes = []
+    L.gmsm_debug_reduce_shape.restype = ctypes.c_int
+    L.gmsm_debug_reduce_shape.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     L.gmsm_multiexp_bases.restype = ctypes.c_int
     L.gmsm_multiexp_bases.argtypes = [ctypes.c_uint64, u64p, sz, ctypes.c_int, u64p]
     L.gmsm_multiexp_bases_device.restype = ctypes.c_int
@@ -249,7 +251,7 @@ def last_error():
 
 # enum gmsm_option (include/gmsm.h)
 OPTIONS = {"window_bits": 0, "tables": 1, "max_run": 2, "host_ranges": 3, "fixed_base_bits": 4, "spin_wait_us": 5, "small_bits": 6, "small_max": 7, "split": 8, "glv": 9, "small_quad": 10,
-           "poly_lane_bits": 11}
+           "poly_lane_bits": 11, "reduce_shape": 12}
 
 
 def set_option(name, value):

@@ -70,6 +70,7 @@ struct Options {
     std::atomic<unsigned> glv{1};              // GMSM_OPT_GLV: half scalars (gmsm_glv.h): 0 never, 1 the fused small-n kernel, 2 the sorted pipeline too
     std::atomic<unsigned> small_quad{0};       // GMSM_OPT_SMALL_QUAD: bucket phase of the fused kernel on lane quads: 0 by size, 1 never (narrow types), 2 always
     std::atomic<unsigned> poly_lane_bits{0};   // GMSM_OPT_POLY_LANE_BITS (tests): 0 = lane width of the suffix scan by length, k in 1..6 = 2^(k-1) coefficients
+    std::atomic<unsigned> reduce_shape{0};     // GMSM_OPT_REDUCE_SHAPE (tests): 0 = the reduction's cost model; packed log2L | levels << 4 | combine kernel << 6
 };
 Options &options();
 
@@ -691,6 +692,7 @@ struct GroupVTable {
     unsigned (*host_piece_ranges)(size_t n, bool with_points);  // point ranges a host-buffer piece of n points runs as
     int (*debug_glv_split)(const uint64_t *scalars, size_t n, uint32_t *out);  // test hook of gmsm_glv.h
     void (*plan_info)(size_t n, unsigned *c, unsigned *nwin, unsigned *entries_per_point, unsigned *fused);  // gmsm_default_plan
+    void (*reduce_shape)(const Context &ctx, uint32_t nw, uint32_t nbuckets, uint32_t out[6]);  // gmsm_debug_reduce_shape
     // KZG opening over the group's scalar field (gmsm_poly.h): polynomials are host (`polys`) or device (`d_polys`) fr.Element
     // vectors, k of them concatenated (lens[i] elements each), never modified
     int (*poly_eval)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,

@@ -1762,6 +1762,16 @@ GMSM_EXPORT int gmsm_default_plan(int group, size_t n, unsigned *c, unsigned *nw
     return GMSM_OK;
 }
 
+GMSM_EXPORT int gmsm_debug_reduce_shape(int group, uint32_t nw, uint32_t nbuckets, uint32_t out[6]) {
+    VT_OR_FAIL(group);
+    if (nw == 0 || nbuckets == 0 || nbuckets > (1u << 19) || !out) return fail(GMSM_ERR_ARG, "gmsm_debug_reduce_shape: nw >= 1, 1 <= nbuckets <= 2^19");
+    Context *ctx;
+    int rc = get_context(&ctx);
+    if (rc) return rc;
+    vt->reduce_shape(*ctx, nw, nbuckets, out);
+    return GMSM_OK;
+}
+
 GMSM_EXPORT unsigned gmsm_num_windows(int group, unsigned c) {
     const GroupVTable *vt = vtable(group);
     return (vt && c) ? num_windows(vt->fr_bits, c) : 0;
@@ -1971,6 +1981,11 @@ GMSM_EXPORT int gmsm_set_option(int key, unsigned value) {
             if (value > 6) return fail(GMSM_ERR_ARG, "GMSM_OPT_POLY_LANE_BITS: 0 (lane width by length) or 1..6 (lanes of 2^(k-1) coefficients)");
             o.poly_lane_bits.store(value);
             return GMSM_OK;
+        case GMSM_OPT_REDUCE_SHAPE:
+            if (value > 255 || (value & 15u) > 8 || ((value >> 4) & 3u) == 1 || ((value >> 6) & 3u) == 3)
+                return fail(GMSM_ERR_ARG, "GMSM_OPT_REDUCE_SHAPE: 0 (the cost model) or log2L (0, 1..8) | levels (0, 2, 3) << 4 | combine kernel (0, 1, 2) << 6");
+            o.reduce_shape.store(value);
+            return GMSM_OK;
         case GMSM_OPT_SPIN_WAIT_US:
             if (value > 1000000) return fail(GMSM_ERR_ARG, "GMSM_OPT_SPIN_WAIT_US: at most 1000000");
             o.spin_wait_us.store(value);
@@ -1994,6 +2009,7 @@ GMSM_EXPORT unsigned gmsm_get_option(int key) {
         case GMSM_OPT_GLV: return o.glv.load();
         case GMSM_OPT_SMALL_QUAD: return o.small_quad.load();
         case GMSM_OPT_POLY_LANE_BITS: return o.poly_lane_bits.load();
+        case GMSM_OPT_REDUCE_SHAPE: return o.reduce_shape.load();
         default: return 0;
     }
 }

@@ -103,7 +103,12 @@ struct Group : GroupHost<F_, FrP_> {
 #define GMSM_COMBINE_WE_WORDS 9
 #endif
     static constexpr bool COMBINE_WE = sizeof(U) <= GMSM_COMBINE_WE_WORDS * 4;
-    static bool use_combine_we(const Context &ctx, uint32_t workgroups) { return COMBINE_WE && workgroups >= 2u * (uint32_t)ctx.num_cus; }
+    // GMSM_OPT_REDUCE_SHAPE (tests) names the combine kernel in bits 6-7: 1 = k_combine_q, 2 = k_combine_we where it is compiled
+    static bool use_combine_we(const Context &ctx, uint32_t workgroups) {
+        const unsigned forced = (options().reduce_shape.load(std::memory_order_relaxed) >> 6) & 3u;
+        if (forced) return COMBINE_WE && forced == 2;
+        return COMBINE_WE && workgroups >= 2u * (uint32_t)ctx.num_cus;
+    }
     // k_fixup_seg: followers a chain head adds itself (one-lane additions); longer chains go to k_fixup_long (quads, one
     // workgroup per chain). Handing chains of 3+ links to the quads for the wide types was measured: no gain at 2^20
     // (BW6-761 fixup 0.75 ms either way - it is 322 K two-link chains in five rounds of 512-register workgroups), and 2^16
@@ -206,8 +211,10 @@ struct Group : GroupHost<F_, FrP_> {
         constexpr size_t SPAN1 = COMBINE_N;  // pairs one combine workgroup takes
         const auto blocks1 = [&](uint32_t l2) { return ((size_t)NB + (SPAN1 << l2) - 1) / (SPAN1 << l2); };
         const auto blocks2 = [&](uint32_t l2) { return (blocks1(l2) + SPAN1 - 1) / SPAN1; };
-        uint32_t log2L = GMSM_TUNE(LOG2L, 0);
-        const uint32_t force_levels = GMSM_TUNE(REDUCE_LEVELS, 0);  // 2 / 3; 0 = cost model
+        // GMSM_OPT_REDUCE_SHAPE (tests; 0 = off): log2L in bits 0-3, the number of levels in bits 4-5
+        const unsigned forced_shape = options().reduce_shape.load(std::memory_order_relaxed);
+        uint32_t log2L = GMSM_TUNE(LOG2L, forced_shape & 15u);
+        const uint32_t force_levels = GMSM_TUNE(REDUCE_LEVELS, (forced_shape >> 4) & 3u);  // 2 / 3; 0 = cost model
         bool three = force_levels == 3;
         if (log2L == 0) {
             // serial kernel: 2L dependent one-lane additions on every SIMD, as many rounds as the threads need;
@@ -257,6 +264,8 @@ struct Group : GroupHost<F_, FrP_> {
             } else {
                 log2L = 8;
             }
+        } else if (three && blocks1(log2L) <= 1) {
+            three = false;  // a forced width with three levels asked for: one combine workgroup leaves nothing for a second level
         }
         if (three) {
             while (blocks2(log2L) > (size_t)RED2_TPB) ++log2L;
@@ -689,6 +698,25 @@ struct Group : GroupHost<F_, FrP_> {
         return GMSM_OK;
     }
 
+    // quads of k_reduce2_q: a power of two, at least 2, that holds the nlast results of the last combine level
+    static uint32_t reduce2_active(uint32_t nlast) {
+        uint32_t active = 2;
+        while (active < nlast) active <<= 1;
+        return active;
+    }
+    // gmsm_debug_reduce_shape: what the reduction of nw bucket sets of NB buckets is launched as under the current options -
+    // log2L, nblocks1, nblocks2, the (first) combine kernel (1 k_combine_q, 2 k_combine_we), the serial kernel (0 one lane,
+    // 1 quads), the quads of k_reduce2_q. (The number of entries only shapes the accumulation.)
+    static void reduce_shape(const Context &ctx, uint32_t nw, uint32_t NB, uint32_t out[6]) {
+        const Geometry q = plan_geometry(ctx, nw, NB, NB);
+        out[0] = q.log2L;
+        out[1] = q.nblocks1;
+        out[2] = q.nblocks2;
+        out[3] = use_combine_we(ctx, q.nblocks1 * nw) ? 2u : 1u;
+        out[4] = SERIAL_QUAD ? 1u : 0u;
+        out[5] = reduce2_active(q.nblocks2 ? q.nblocks2 : q.nblocks1);
+    }
+
     // The three kernels of the bucket reduction: buckets (nw x NB lazy records; starts == nullptr: every record is
     // stored, infinity as zz = 0) -> ws.totals. Scratch: ws.red_pre, ws.partials.
     static void enqueue_reduce_kernels(Context &ctx, Workspace &ws, const Geometry &q, uint32_t T, const void *buckets,
@@ -735,8 +763,7 @@ struct Group : GroupHost<F_, FrP_> {
             nlast = q.nblocks2;
             rest = 0;
         }
-        uint32_t active = 2;
-        while (active < nlast) active <<= 1;
+        const uint32_t active = reduce2_active(nlast);
         hipLaunchKernelGGL((k_reduce2_q<U, true>), dim3(nw), dim3(4 * active), 2 * active * sizeof(QRec<U>), stream, last, nlast,
                            rest, active, totals);
         (void)ctx;

@@ -174,6 +174,7 @@ struct VTableOf {
         const WindowPlan p = G::plan_for(nullptr, n);
         *c = p.c, *nwin = p.nwin_total, *entries_per_point = p.glv ? 2u : 1u, *fused = 0u;
     }
+    static void reduce_shape(const Context &ctx, uint32_t nw, uint32_t nbuckets, uint32_t out[6]) { G::reduce_shape(ctx, nw, nbuckets, out); }
     static int debug_field_op(int field, int op, const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out) {
         using BaseP = typename G::F::Params;
         if (field == 0) {
@@ -510,7 +511,7 @@ struct VTableOf {
         static const GroupVTable vt = {G::FR_BITS,      G::AFF_BYTES,   G::SCALAR_BYTES, sizeof(typename G::J),
                                        sizeof(typename G::Ext), &multiexp_host, &multiexp_device, &window_sums,
                                        &fold,           &jac_to_affine, &debug_decompose, &debug_field_op,
-                                       &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info,
+                                       &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info, &reduce_shape,
                                        &poly_eval, &poly_div, &kzg_open, lagrange_entry(),
                                        &fflonk_next_divisor, &open_check, &fflonk_fold, open_w_entry(), open_wprime_entry(), &batch_scale, &linear_combinations,
                                        (unsigned)G::FrP::MAX_ORDER};

@@ -360,6 +360,15 @@ class _Group:
             raise RuntimeError(self._error(rc))
         return {"window_bits": v[0].value, "windows": v[1].value, "entries_per_point": v[2].value, "fused": bool(v[3].value)}
 
+    def reduce_shape(self, nw, nbuckets):
+        """gmsm_debug_reduce_shape: what the bucket reduction over nw bucket sets of nbuckets buckets is launched as under the
+        current options: dict(log2L, nblocks1, nblocks2, combine (1 k_combine_q, 2 k_combine_we), serial_quad, active)."""
+        v = (_lib.ctypes.c_uint32 * 6)()
+        rc = _lib.load().gmsm_debug_reduce_shape(self.gid, nw, nbuckets, v)
+        if rc:
+            raise RuntimeError(self._error(rc))
+        return {"log2L": v[0], "nblocks1": v[1], "nblocks2": v[2], "combine": v[3], "serial_quad": v[4], "active": v[5]}
+
     def num_windows(self, c):
         return int(_lib.load().gmsm_num_windows(self.gid, c))
 

@@ -469,6 +469,11 @@ int gmsm_debug_field_op(int group, int field, int op, const uint64_t *a, const u
  * group law of the pipeline. */
 int gmsm_debug_group_op(int group, int op, const uint64_t *acc, const uint64_t *pts_or_acc2, size_t count, uint64_t *out);
 
+/* the launch shape of the bucket reduction over nw bucket sets of nbuckets buckets on the calling thread's device, under the
+ * current options: out = {log2L, level-1 workgroups per set, workgroups of the second combine (0 = two levels), the combine
+ * kernel of level 1 (1 k_combine_q, 2 k_combine_we), the serial kernel (0 one lane, 1 lane quads), the quads of k_reduce2_q} */
+int gmsm_debug_reduce_shape(int group, uint32_t nw, uint32_t nbuckets, uint32_t out[6]);
+
 /* ---- utilities ---- */
 /* out_points[i] = [k0 + i*k1] * base, i < n (affine, Go layout). k0,k1: plain (non-Montgomery) little-endian limbs.
  * Host-side, nthreads worker threads. For building SRS-like synthetic bases (cf. BatchScalarMultiplicationG1,
@@ -490,7 +495,8 @@ int gmsm_get_stage_launches(unsigned long *out_launches, int max_stages);
 /* ---- switches (process-wide).  GMSM_OPT_WINDOW_BITS and GMSM_OPT_TABLES take their initial value from the environment
  *      variables GMSM_C / GMSM_TABLES once, when the library is first used; nothing reads the environment per call.
  *      GMSM_OPT_MAX_RUN / GMSM_OPT_HOST_RANGES exist for the tests of the point-range splits (0 = off),
- *      GMSM_OPT_POLY_LANE_BITS for the tests of the polynomial scan's launch shapes (0 = off). ---- */
+ *      GMSM_OPT_POLY_LANE_BITS for the tests of the polynomial scan's launch shapes (0 = off),
+ *      GMSM_OPT_REDUCE_SHAPE for the tests of the bucket reduction's launch shapes (0 = off). ---- */
 enum gmsm_option {
     GMSM_OPT_WINDOW_BITS = 0, /* 0 = the library's measured table per group and size, 2..20 = forced (cost only: the
                                  affine result does not depend on c, multiexp_test.go:95-126) */
@@ -520,11 +526,17 @@ enum gmsm_option {
                                  (tests/test_gpu_glv.py::test_glv_off_is_the_integer_combination_outside_the_subgroup) */
     GMSM_OPT_SMALL_QUAD = 10, /* bucket phase of the fused small-n kernel on lane quads: 0 (default) by call size, 1 never,
                                  2 always (the Fp2 groups and BW6-761 always run it on quads) */
-    GMSM_OPT_POLY_LANE_BITS = 11 /* for the tests of the suffix scan behind gmsm_poly_eval, gmsm_poly_div_x_minus_a, the gmsm_kzg_open
+    GMSM_OPT_POLY_LANE_BITS = 11, /* for the tests of the suffix scan behind gmsm_poly_eval, gmsm_poly_div_x_minus_a, the gmsm_kzg_open
                                  and the gmsm_shplonk_open entries: 0 (default) = lanes of 8, 16 or 32 coefficients by length; k in 1..6 =
                                  lanes of 2^(k-1) coefficients whatever the length (a tile is 256 lanes, so k = 1 reaches the
                                  carry pass's lanes of several tiles at 2^16 coefficients instead of 2^21). Cost only: every
                                  output is the same field element. Read once per call. */
+    GMSM_OPT_REDUCE_SHAPE = 12 /* for the tests of the bucket reduction's launch shapes: 0 (default) = the cost model. A packed value:
+                                 bits 0-3 log2L (1..8 buckets per serial segment as a power of two, 0 = model), bits 4-5 the levels
+                                 (2 = serial, combine, level 2; 3 = a second combine in between; 0 = model), bits 6-7 the combine kernel
+                                 (1 = k_combine_q, 2 = k_combine_we where the group has it, 0 = by workgroup count). The planner still
+                                 raises log2L until the last level holds its blocks, and runs two levels where three cannot be formed.
+                                 Cost only: every window total is the same group element. gmsm_debug_reduce_shape reports the outcome. */
 };
 int gmsm_set_option(int key, unsigned value);
 unsigned gmsm_get_option(int key);

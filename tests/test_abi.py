@@ -223,6 +223,25 @@ def test_poly_lane_bits_option_needs_no_device(gm):
         assert gm.get_option("poly_lane_bits") == 0
 
 
+def test_reduce_shape_option_needs_no_device(gm):
+    """GMSM_OPT_REDUCE_SHAPE: 0 (the default, the cost model) or log2L (0, 1..8) | levels (0, 2, 3) << 4 | combine kernel
+    (0, 1, 2) << 6; every other value is the argument error and leaves the option as it was"""
+    assert gm._lib.OPTIONS["reduce_shape"] == 12 and gm.get_option("reduce_shape") == 0
+    good = [l | lv << 4 | k << 6 for l in range(0, 9) for lv in (0, 2, 3) for k in (0, 1, 2)]
+    assert len(good) == 81
+    for v in good:
+        with gm.options(reduce_shape=v):
+            assert gm.get_option("reduce_shape") == v
+        assert gm.get_option("reduce_shape") == 0
+    lib = gm._lib.load()
+    for bad in sorted(set(range(0, 256)) - set(good)) + [256, 257, 1 << 12, 2**32 - 1]:
+        with pytest.raises(ValueError, match=r"GMSM_OPT_REDUCE_SHAPE: 0 .* log2L .* levels .* combine kernel"):
+            gm.set_option("reduce_shape", bad)
+        assert lib.gmsm_set_option(gm._lib.OPTIONS["reduce_shape"], bad) == gm._lib.GMSM_ERR_ARG
+        assert gm.get_option("reduce_shape") == 0
+    assert lib.gmsm_debug_reduce_shape(99, 1, 64, (ctypes.c_uint32 * 6)()) == gm._lib.GMSM_ERR_ARG
+
+
 def test_race_client_builds_as_c(tmp_path):
     """tests/c/race_client.c (the sanitizer workload) is plain C99 + pthreads against include/gmsm.h and links to the shipped
     library; without a device it says so and exits 77."""

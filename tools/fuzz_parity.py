@@ -120,7 +120,7 @@ def main():
             if err is not None or not (back == both).all():
                 bad += 1
                 print("COMPRESSED ROUND TRIP MISMATCH", dict(n=n, err=err), flush=True)
-    for k in ("small_bits", "small_max", "split", "small_quad", "poly_lane_bits"):
+    for k in ("small_bits", "small_max", "split", "small_quad", "poly_lane_bits", "reduce_shape"):
         gm.set_option(k, 0)
     gm.set_option("glv", 1)
     for h in handles:
