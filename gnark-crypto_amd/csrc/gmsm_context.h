@@ -444,6 +444,33 @@ static inline int order_after(Workspace &ws, hipStream_t caller) {
     return GMSM_OK;
 }
 
+// An input that the caller gives on the host or on the device (exactly one of the two; none when bytes == 0). A host
+// vector is copied into `stage` on the workspace's stream; a device vector is read where it is, after what `after` names:
+// the work queued on the caller's stream, everything on the device (the entries that take no stream: the vector may
+// still be being written on a stream we do not know), or nothing (the call site orders several vectors at once).
+// bytes == 0 does nothing at all - no copy, no ordering - and hands back `dev`: an entry that may be given an empty vector
+// and still needs the ordering does it itself (today every caller but gmsm_bases_register and batch_scalar_mul refuses or
+// returns on an empty input before it gets here).
+struct After {
+    enum { NOTHING, STREAM, DEVICE } what;
+    hipStream_t stream = nullptr;  // STREAM: the caller's (NULL = the device's default stream)
+};
+template <class T>
+static inline int stage_input(Workspace &ws, DeviceBuffer &stage, const void *host, T *dev, size_t bytes, After after, T **out) {
+    *out = dev;
+    if (!bytes) return GMSM_OK;
+    if (host) {
+        if (int rc = stage.ensure(bytes)) return rc;
+        HIP_TRY(hipMemcpyAsync(stage.ptr, host, bytes, hipMemcpyHostToDevice, ws.stream));
+        *out = stage.ptr;
+    } else if (after.what == After::STREAM) {
+        return order_after(ws, after.stream);
+    } else if (after.what == After::DEVICE) {
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    return GMSM_OK;
+}
+
 // Scratch of a workspace is reused by every call that leases it; calls may run on different streams (the workspace's
 // own, or the caller's for the enqueue-only entry). begin_use orders `stream` behind the last work enqueued on the
 // workspace, end_use publishes the end of this call's work.

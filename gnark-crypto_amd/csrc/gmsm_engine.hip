@@ -103,6 +103,78 @@ int get_context_of_pointer(const void *p, Context **out) {
     return get_context(out);
 }
 
+// How an entry starts: the context of the calling thread's device, of a given device (the bases or the domain decide it),
+// or of the device that owns a pointer - with that device made the calling thread's current one.
+static int select_device(int rc, Context *const *ctx) {
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice((*ctx)->device));
+    return GMSM_OK;
+}
+static int enter(Context **ctx) { return select_device(get_context(ctx), ctx); }
+static int enter_on(int device, Context **ctx) { return select_device(get_context_for(device, ctx), ctx); }
+static int enter_owner(const void *p, Context **ctx) { return select_device(get_context_of_pointer(p, ctx), ctx); }
+
+// Handles are index + 1 into a table that only grows: a slot that was released, or emptied by gmsm_shutdown, stays (null),
+// so an old handle stays unknown and never comes to name a later registration. A reference handed out keeps the object
+// alive for the caller's whole call (or ticket) even if another thread releases the handle meanwhile.
+template <class T>
+struct HandleTable {
+    std::mutex mu;
+    std::vector<std::shared_ptr<T>> slots;
+    uint64_t add(std::shared_ptr<T> p) {
+        std::lock_guard<std::mutex> lk(mu);
+        slots.push_back(std::move(p));
+        return slots.size();
+    }
+    std::shared_ptr<T> get(uint64_t handle) {
+        std::lock_guard<std::mutex> lk(mu);
+        return handle == 0 || handle > slots.size() ? nullptr : slots[handle - 1];
+    }
+    std::shared_ptr<T> take(uint64_t handle) {  // the table's reference: null when the handle names nothing (any more)
+        std::shared_ptr<T> p;
+        std::lock_guard<std::mutex> lk(mu);
+        if (handle != 0 && handle <= slots.size()) p.swap(slots[handle - 1]);
+        return p;
+    }
+    std::vector<std::shared_ptr<T>> drain() {  // every reference, the length kept
+        std::vector<std::shared_ptr<T>> all;
+        std::lock_guard<std::mutex> lk(mu);
+        all.resize(slots.size());
+        all.swap(slots);
+        return all;
+    }
+};
+
+// fn(i) -> return code for every i < count, each on a thread of its own; the first index that failed, with its code and
+// its thread's error text (rc == GMSM_OK: none did). An index whose thread cannot be started fails with GMSM_ERR_DEVICE:
+// nothing is thrown past the threads already running, or past the C ABI.
+struct Failure {
+    size_t index = 0;
+    int rc = GMSM_OK;
+    std::string err;
+};
+template <class F>
+static Failure on_threads(size_t count, F fn) {
+    std::vector<Failure> res(count);
+    std::vector<std::thread> th;
+    th.reserve(count);
+    for (size_t i = 0; i < count; ++i) {
+        res[i].index = i;
+        try {
+            th.emplace_back([&res, &fn, i] {
+                if ((res[i].rc = fn(i))) res[i].err = gmsm_last_error();
+            });
+        } catch (const std::exception &e) {
+            res[i].rc = GMSM_ERR_DEVICE;
+            res[i].err = std::string("cannot start the worker: ") + e.what();
+        }
+    }
+    for (auto &t : th) t.join();
+    for (Failure &r : res)
+        if (r.rc) return r;
+    return Failure();
+}
+
 const GroupVTable *gmsm_vtable_bn254_g1();
 const GroupVTable *gmsm_vtable_bn254_g2();
 const GroupVTable *gmsm_vtable_bls12_381_g1();
@@ -218,6 +290,17 @@ struct EnvDevices {
     std::vector<int> list;
     std::string err;
 };
+static void every_device(int ndev, std::vector<int> &out) {
+    for (int d = 0; d < ndev; ++d) out.push_back(d);
+}
+// every listed device exists; `what` is the entry (or "sharded MultiExp") the text starts with
+static int devices_exist(const char *what, const int *devs, size_t count, int ndev) {
+    for (size_t i = 0; i < count; ++i)
+        if (devs[i] < 0 || devs[i] >= ndev)
+            return fail(GMSM_ERR_DEVICE, std::string(what) + ": device " + std::to_string(devs[i]) + " does not exist (" +
+                                             std::to_string(ndev) + " visible)");
+    return GMSM_OK;
+}
 static const EnvDevices &env_devices() {
     static const EnvDevices *e = [] {
         EnvDevices *x = new EnvDevices();
@@ -229,7 +312,7 @@ static const EnvDevices &env_devices() {
             return x;
         }
         if (strcmp(v, "all") == 0) {
-            for (int d = 0; d < ndev; ++d) x->list.push_back(d);
+            every_device(ndev, x->list);
             return x;
         }
         for (const char *p = v; *p;) {
@@ -429,12 +512,9 @@ GMSM_EXPORT int gmsm_multiexp_sharded(int group, const uint64_t *points, size_t 
     if (devs.empty()) {  // nothing configured: the caller asked for a sharded call, so every visible device
         int ndev = gmsm_device_count();
         if (ndev <= 0) return fail(GMSM_ERR_DEVICE, "no usable HIP device; libgmsm has no CPU fallback");
-        for (int d = 0; d < ndev; ++d) devs.push_back(d);
+        every_device(ndev, devs);
     }
-    const int ndev = gmsm_device_count();
-    for (int d : devs)
-        if (d < 0 || d >= ndev)
-            return fail(GMSM_ERR_DEVICE, "sharded MultiExp: device " + std::to_string(d) + " does not exist (" + std::to_string(ndev) + " visible)");
+    if ((rc = devices_exist("sharded MultiExp", devs.data(), devs.size(), gmsm_device_count()))) return rc;
     return multiexp_sharded_run(group, points, nullptr, scalars, n_points, devs, mode, out_jac);
 }
 
@@ -495,23 +575,26 @@ GMSM_EXPORT int gmsm_multiexp_device(int group, const void *d_points, const void
                                      uint64_t *out_jac) {
     VT_OR_FAIL(group);
     Context *ctx;
-    int rc = get_context_of_pointer(d_scalars ? d_scalars : d_points, &ctx);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = enter_owner(d_scalars ? d_scalars : d_points, &ctx)) return rc;
     return vt->multiexp_device(*ctx, d_points, d_scalars, n, (hipStream_t)hip_stream, out_jac, nullptr);
 }
 
 // ------------------------------------------------------------------ resident bases
 using BasesRef = std::shared_ptr<ResidentBases>;
-static std::mutex g_bases_mu;
-static std::vector<BasesRef> g_bases;  // handle = index + 1
+// g_bases and g_sharded (below) each have their lock: no entry looks at both tables under one lock - gmsm_bases_release takes
+// from the one its handle's tag names - and gmsm_shutdown, which empties both, runs alone by its contract.
+static HandleTable<ResidentBases> g_bases;
 
-// The returned reference keeps the bases alive for the caller's whole call (or ticket) even if another thread releases
-// the handle meanwhile.
-static BasesRef lookup_bases(uint64_t handle) {
-    std::lock_guard<std::mutex> lk(g_bases_mu);
-    if (handle == 0 || handle > g_bases.size()) return nullptr;
-    return g_bases[handle - 1];
+// new bases of `group` on the call's device from n affine points in device memory, and their handle
+static int register_device_points(const GroupVTable *vt, Context *ctx, Workspace &ws, int group, const void *d_points,
+                                  size_t n, uint64_t *out_handle) {
+    BasesRef rb = std::make_shared<ResidentBases>();
+    rb->group = group;
+    rb->device = ctx->device;
+    int rc = vt->register_bases(*ctx, d_points, n, ws.stream, rb.get());
+    if (rc) return rc;  // ~ResidentBases frees whatever was allocated
+    *out_handle = g_bases.add(rb);
+    return GMSM_OK;
 }
 
 GMSM_EXPORT int gmsm_bases_register(int group, const uint64_t *points, const void *d_points, size_t n,
@@ -521,81 +604,89 @@ GMSM_EXPORT int gmsm_bases_register(int group, const uint64_t *points, const voi
     if ((points == nullptr) == (d_points == nullptr) && n)
         return fail(GMSM_ERR_ARG, "gmsm_bases_register: give exactly one of points (host) / d_points (device)");
     Context *ctx;
-    int rc = get_context_of_pointer(d_points, &ctx);
+    int rc = enter_owner(d_points, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     Workspace &ws = *lease.w;
-    const void *src = d_points;
-    if (points && n) {
-        if ((rc = ws.h2d_points.ensure(n * vt->aff_bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, points, n * vt->aff_bytes, hipMemcpyHostToDevice, ws.stream));
-        src = ws.h2d_points.ptr;
-    } else if (n) {
-        HIP_TRY(hipDeviceSynchronize());  // d_points may still be being written on a stream we do not know
-    }
-    BasesRef rb = std::make_shared<ResidentBases>();
-    rb->group = group;
-    rb->device = ctx->device;
-    rc = vt->register_bases(*ctx, src, n, ws.stream, rb.get());
-    if (rc) return rc;  // ~ResidentBases frees whatever was allocated
-    std::lock_guard<std::mutex> lk2(g_bases_mu);
-    g_bases.push_back(rb);
-    *out_handle = g_bases.size();
-    return GMSM_OK;
+    const void *src;
+    if ((rc = stage_input(ws, ws.h2d_points, points, d_points, n * vt->aff_bytes, {After::DEVICE}, &src))) return rc;
+    return register_device_points(vt, ctx, ws, group, src, n, out_handle);
 }
 
 // ------------------------------------------------------------------ point ingest
-static int point_error(const char *what, long long index, uint32_t status) {
-    return fail(GMSM_ERR_POINT, std::string(what) + ": point " + std::to_string(index) + ": " + point_status_text(status));
+// what a decode or a validation found: GMSM_OK, or the first offender's position in *bad_index and its status as the text
+static int point_result(const char *what, long long bad, uint32_t status, int64_t *bad_index) {
+    if (bad < 0) return GMSM_OK;
+    *bad_index = bad;
+    return fail(GMSM_ERR_POINT, std::string(what) + ": point " + std::to_string(bad) + ": " + point_status_text(status));
 }
 
-static int register_device_points(const GroupVTable *vt, Context *ctx, Workspace &ws, int group, const void *d_points,
-                                  size_t n, uint64_t *out_handle) {
-    BasesRef rb = std::make_shared<ResidentBases>();
-    rb->group = group;
-    rb->device = ctx->device;
-    int rc = vt->register_bases(*ctx, d_points, n, ws.stream, rb.get());
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk2(g_bases_mu);
-    g_bases.push_back(rb);
-    *out_handle = g_bases.size();
-    return GMSM_OK;
-}
+// The two wire formats of the ingest entries: RawBytes() output (X and Y), and the Encoder's default, compressed, format: X
+// and the flag of Y's half (gmsm_decompress.h), half the bytes.
+struct WireFormat {
+    const char *arg;  // the entries' name for the encoded bytes
+    size_t shrink;    // encoded bytes of a point = aff_bytes / shrink
+    decltype(GroupVTable::decode_raw) GroupVTable::*decode;
+};
+static const WireFormat WIRE_RAW = {"raw", 1, &GroupVTable::decode_raw}, WIRE_COMPRESSED = {"comp", 2, &GroupVTable::decode_compressed};
 
-GMSM_EXPORT int gmsm_points_from_raw(int group, const uint8_t *raw, size_t n, int check, uint64_t *out_affine,
-                                     void *d_out_affine, int64_t *bad_index) {
+static int points_decode(const char *E, const WireFormat &wire, int group, const uint8_t *enc, size_t n, int check, uint64_t *out_affine,
+                         void *d_out_affine, int64_t *bad_index) {
     VT_OR_FAIL(group);
-    if (!bad_index) return fail(GMSM_ERR_ARG, "gmsm_points_from_raw: bad_index is null");
+    if (!bad_index) return fail(GMSM_ERR_ARG, std::string(E) + ": bad_index is null");
     *bad_index = -1;
-    if (n && (!raw || (!out_affine && !d_out_affine))) return fail(GMSM_ERR_ARG, "gmsm_points_from_raw: null argument");
+    if (n && (!enc || (!out_affine && !d_out_affine))) return fail(GMSM_ERR_ARG, std::string(E) + ": null argument");
     if (n == 0) return GMSM_OK;
     Context *ctx;
-    int rc = get_context_of_pointer(d_out_affine, &ctx);
+    int rc = enter_owner(d_out_affine, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     Workspace &ws = *lease.w;
-    const size_t bytes = n * vt->aff_bytes;
-    if ((rc = ws.raw_bytes.ensure(bytes))) return rc;
+    const size_t bytes = n * vt->aff_bytes, ebytes = bytes / wire.shrink;
+    if ((rc = ws.raw_bytes.ensure(ebytes))) return rc;
     void *d_out = d_out_affine;
     if (!d_out) {
         if ((rc = ws.h2d_points.ensure(bytes))) return rc;
         d_out = ws.h2d_points.ptr;
     }
-    HIP_TRY(hipMemcpyAsync(ws.raw_bytes.ptr, raw, bytes, hipMemcpyHostToDevice, ws.stream));
+    HIP_TRY(hipMemcpyAsync(ws.raw_bytes.ptr, enc, ebytes, hipMemcpyHostToDevice, ws.stream));
     long long bad = -1;
     uint32_t status = 0;
-    if ((rc = vt->decode_raw(ws, ws.raw_bytes.ptr, n, check, d_out, &bad, &status))) return rc;
+    if ((rc = (vt->*wire.decode)(ws, ws.raw_bytes.ptr, n, check, d_out, &bad, &status))) return rc;
     if (out_affine) {
         HIP_TRY(hipMemcpyAsync(out_affine, d_out, bytes, hipMemcpyDeviceToHost, ws.stream));
         HIP_TRY(hipStreamSynchronize(ws.stream));
     }
-    if (bad >= 0) {
-        *bad_index = bad;
-        return point_error("gmsm_points_from_raw", bad, status);
+    return point_result(E, bad, status, bad_index);
+}
+
+static int bases_register_encoded(const char *E, const WireFormat &wire, int group, const uint8_t *enc, size_t n, int check,
+                                  uint64_t *out_handle, int64_t *bad_index) {
+    VT_OR_FAIL(group);
+    if (!out_handle || !bad_index) return fail(GMSM_ERR_ARG, std::string(E) + ": null argument");
+    *bad_index = -1;
+    if (n && !enc) return fail(GMSM_ERR_ARG, std::string(E) + ": " + wire.arg + " is null");
+    Context *ctx;
+    int rc = enter(&ctx);
+    if (rc) return rc;
+    GMSM_LEASE_OR_FAIL(lease, *ctx);
+    Workspace &ws = *lease.w;
+    const size_t bytes = n * vt->aff_bytes, ebytes = bytes / wire.shrink;
+    if (n) {
+        if ((rc = ws.raw_bytes.ensure(ebytes))) return rc;
+        if ((rc = ws.h2d_points.ensure(bytes))) return rc;
+        HIP_TRY(hipMemcpyAsync(ws.raw_bytes.ptr, enc, ebytes, hipMemcpyHostToDevice, ws.stream));
+        long long bad = -1;
+        uint32_t status = 0;
+        if ((rc = (vt->*wire.decode)(ws, ws.raw_bytes.ptr, n, check, ws.h2d_points.ptr, &bad, &status))) return rc;
+        if ((rc = point_result(E, bad, status, bad_index))) return rc;
     }
-    return GMSM_OK;
+    return register_device_points(vt, ctx, ws, group, ws.h2d_points.ptr, n, out_handle);
+}
+
+GMSM_EXPORT int gmsm_points_from_raw(int group, const uint8_t *raw, size_t n, int check, uint64_t *out_affine,
+                                     void *d_out_affine, int64_t *bad_index) {
+    return points_decode("gmsm_points_from_raw", WIRE_RAW, group, raw, n, check, out_affine, d_out_affine, bad_index);
 }
 
 GMSM_EXPORT int gmsm_points_validate(int group, const uint64_t *points, const void *d_points, size_t n, int check,
@@ -607,91 +698,26 @@ GMSM_EXPORT int gmsm_points_validate(int group, const uint64_t *points, const vo
         return fail(GMSM_ERR_ARG, "gmsm_points_validate: give exactly one of points (host) / d_points (device)");
     if (n == 0 || check <= 0) return GMSM_OK;
     Context *ctx;
-    int rc = get_context_of_pointer(d_points, &ctx);
+    int rc = enter_owner(d_points, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     Workspace &ws = *lease.w;
-    const void *src = d_points;
-    if (points) {
-        if ((rc = ws.h2d_points.ensure(n * vt->aff_bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, points, n * vt->aff_bytes, hipMemcpyHostToDevice, ws.stream));
-        src = ws.h2d_points.ptr;
-    } else {
-        HIP_TRY(hipDeviceSynchronize());  // d_points may still be being written on a stream we do not know
-    }
+    const void *src;
+    if ((rc = stage_input(ws, ws.h2d_points, points, d_points, n * vt->aff_bytes, {After::DEVICE}, &src))) return rc;
     long long bad = -1;
     uint32_t status = 0;
     if ((rc = vt->validate_points(ws, src, n, check, &bad, &status))) return rc;
-    if (bad >= 0) {
-        *bad_index = bad;
-        return point_error("gmsm_points_validate", bad, status);
-    }
-    return GMSM_OK;
+    return point_result("gmsm_points_validate", bad, status, bad_index);
 }
 
 GMSM_EXPORT int gmsm_bases_register_raw(int group, const uint8_t *raw, size_t n, int check, uint64_t *out_handle,
                                         int64_t *bad_index) {
-    VT_OR_FAIL(group);
-    if (!out_handle || !bad_index) return fail(GMSM_ERR_ARG, "gmsm_bases_register_raw: null argument");
-    *bad_index = -1;
-    if (n && !raw) return fail(GMSM_ERR_ARG, "gmsm_bases_register_raw: raw is null");
-    Context *ctx;
-    int rc = get_context(&ctx);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    GMSM_LEASE_OR_FAIL(lease, *ctx);
-    Workspace &ws = *lease.w;
-    const size_t bytes = n * vt->aff_bytes;
-    if (n) {
-        if ((rc = ws.raw_bytes.ensure(bytes))) return rc;
-        if ((rc = ws.h2d_points.ensure(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws.raw_bytes.ptr, raw, bytes, hipMemcpyHostToDevice, ws.stream));
-        long long bad = -1;
-        uint32_t status = 0;
-        if ((rc = vt->decode_raw(ws, ws.raw_bytes.ptr, n, check, ws.h2d_points.ptr, &bad, &status))) return rc;
-        if (bad >= 0) {
-            *bad_index = bad;
-            return point_error("gmsm_bases_register_raw", bad, status);
-        }
-    }
-    return register_device_points(vt, ctx, ws, group, ws.h2d_points.ptr, n, out_handle);
+    return bases_register_encoded("gmsm_bases_register_raw", WIRE_RAW, group, raw, n, check, out_handle, bad_index);
 }
 
-// The Encoder's default (compressed) format: X and the flag of Y's half (gmsm_decompress.h). Same shape as the raw entries.
 GMSM_EXPORT int gmsm_points_from_compressed(int group, const uint8_t *comp, size_t n, int check, uint64_t *out_affine,
                                             void *d_out_affine, int64_t *bad_index) {
-    VT_OR_FAIL(group);
-    if (!bad_index) return fail(GMSM_ERR_ARG, "gmsm_points_from_compressed: bad_index is null");
-    *bad_index = -1;
-    if (n && (!comp || (!out_affine && !d_out_affine))) return fail(GMSM_ERR_ARG, "gmsm_points_from_compressed: null argument");
-    if (n == 0) return GMSM_OK;
-    Context *ctx;
-    int rc = get_context_of_pointer(d_out_affine, &ctx);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    GMSM_LEASE_OR_FAIL(lease, *ctx);
-    Workspace &ws = *lease.w;
-    const size_t bytes = n * vt->aff_bytes, cbytes = bytes / 2;
-    if ((rc = ws.raw_bytes.ensure(cbytes))) return rc;
-    void *d_out = d_out_affine;
-    if (!d_out) {
-        if ((rc = ws.h2d_points.ensure(bytes))) return rc;
-        d_out = ws.h2d_points.ptr;
-    }
-    HIP_TRY(hipMemcpyAsync(ws.raw_bytes.ptr, comp, cbytes, hipMemcpyHostToDevice, ws.stream));
-    long long bad = -1;
-    uint32_t status = 0;
-    if ((rc = vt->decode_compressed(ws, ws.raw_bytes.ptr, n, check, d_out, &bad, &status))) return rc;
-    if (out_affine) {
-        HIP_TRY(hipMemcpyAsync(out_affine, d_out, bytes, hipMemcpyDeviceToHost, ws.stream));
-        HIP_TRY(hipStreamSynchronize(ws.stream));
-    }
-    if (bad >= 0) {
-        *bad_index = bad;
-        return point_error("gmsm_points_from_compressed", bad, status);
-    }
-    return GMSM_OK;
+    return points_decode("gmsm_points_from_compressed", WIRE_COMPRESSED, group, comp, n, check, out_affine, d_out_affine, bad_index);
 }
 
 GMSM_EXPORT int gmsm_points_compress(int group, const uint64_t *points, const void *d_points, size_t n, uint8_t *out_comp) {
@@ -700,21 +726,14 @@ GMSM_EXPORT int gmsm_points_compress(int group, const uint64_t *points, const vo
         return fail(GMSM_ERR_ARG, "gmsm_points_compress: give exactly one of points (host) / d_points (device), and out_comp");
     if (n == 0) return GMSM_OK;
     Context *ctx;
-    int rc = get_context_of_pointer(d_points, &ctx);
+    int rc = enter_owner(d_points, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     Workspace &ws = *lease.w;
     const size_t bytes = n * vt->aff_bytes, cbytes = bytes / 2;
     if ((rc = ws.raw_bytes.ensure(cbytes))) return rc;
-    const void *src = d_points;
-    if (points) {
-        if ((rc = ws.h2d_points.ensure(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, points, bytes, hipMemcpyHostToDevice, ws.stream));
-        src = ws.h2d_points.ptr;
-    } else {
-        HIP_TRY(hipDeviceSynchronize());  // d_points may still be being written on a stream we do not know
-    }
+    const void *src;
+    if ((rc = stage_input(ws, ws.h2d_points, points, d_points, bytes, {After::DEVICE}, &src))) return rc;
     if ((rc = vt->encode_compressed(ws, src, n, ws.raw_bytes.ptr))) return rc;
     HIP_TRY(hipMemcpyAsync(out_comp, ws.raw_bytes.ptr, cbytes, hipMemcpyDeviceToHost, ws.stream));
     HIP_TRY(hipStreamSynchronize(ws.stream));
@@ -723,30 +742,7 @@ GMSM_EXPORT int gmsm_points_compress(int group, const uint64_t *points, const vo
 
 GMSM_EXPORT int gmsm_bases_register_compressed(int group, const uint8_t *comp, size_t n, int check, uint64_t *out_handle,
                                                int64_t *bad_index) {
-    VT_OR_FAIL(group);
-    if (!out_handle || !bad_index) return fail(GMSM_ERR_ARG, "gmsm_bases_register_compressed: null argument");
-    *bad_index = -1;
-    if (n && !comp) return fail(GMSM_ERR_ARG, "gmsm_bases_register_compressed: comp is null");
-    Context *ctx;
-    int rc = get_context(&ctx);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    GMSM_LEASE_OR_FAIL(lease, *ctx);
-    Workspace &ws = *lease.w;
-    const size_t bytes = n * vt->aff_bytes;
-    if (n) {
-        if ((rc = ws.raw_bytes.ensure(bytes / 2))) return rc;
-        if ((rc = ws.h2d_points.ensure(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws.raw_bytes.ptr, comp, bytes / 2, hipMemcpyHostToDevice, ws.stream));
-        long long bad = -1;
-        uint32_t status = 0;
-        if ((rc = vt->decode_compressed(ws, ws.raw_bytes.ptr, n, check, ws.h2d_points.ptr, &bad, &status))) return rc;
-        if (bad >= 0) {
-            *bad_index = bad;
-            return point_error("gmsm_bases_register_compressed", bad, status);
-        }
-    }
-    return register_device_points(vt, ctx, ws, group, ws.h2d_points.ptr, n, out_handle);
+    return bases_register_encoded("gmsm_bases_register_compressed", WIRE_COMPRESSED, group, comp, n, check, out_handle, bad_index);
 }
 
 GMSM_EXPORT int gmsm_bases_register_dump(int group, const char *path, uint64_t offset, int expect_marker, size_t max_points,
@@ -782,9 +778,8 @@ GMSM_EXPORT int gmsm_bases_register_dump(int group, const char *path, uint64_t o
         }
     }
     Context *ctx;
-    int rc = get_context(&ctx);
+    int rc = enter(&ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     Workspace &ws = *lease.w;
     const size_t bytes = n * vt->aff_bytes;
@@ -832,10 +827,7 @@ GMSM_EXPORT int gmsm_bases_register_dump(int group, const char *path, uint64_t o
             long long bad = -1;
             uint32_t status = 0;
             if ((rc = vt->validate_points(ws, ws.h2d_points.ptr, n, check, &bad, &status))) return rc;
-            if (bad >= 0) {
-                *bad_index = bad;
-                return point_error("gmsm_bases_register_dump", bad, status);
-            }
+            if ((rc = point_result("gmsm_bases_register_dump", bad, status, bad_index))) return rc;
         }
     }
     if ((rc = register_device_points(vt, ctx, ws, group, ws.h2d_points.ptr, n, out_handle))) return rc;
@@ -852,13 +844,10 @@ struct ShardedBases {
     std::map<int, std::shared_ptr<ResidentBases>> replicas;    // device -> its copy
 };
 constexpr uint64_t SHARDED_TAG = (uint64_t)1 << 62;
-static std::vector<std::shared_ptr<ShardedBases>> g_sharded;  // handle = SHARDED_TAG | (index + 1); under g_bases_mu
+static HandleTable<ShardedBases> g_sharded;  // handle = SHARDED_TAG | the table's
 
 static std::shared_ptr<ShardedBases> lookup_sharded(uint64_t handle) {
-    std::lock_guard<std::mutex> lk(g_bases_mu);
-    const uint64_t i = handle & ~SHARDED_TAG;
-    if (!(handle & SHARDED_TAG) || i == 0 || i > g_sharded.size()) return nullptr;
-    return g_sharded[i - 1];
+    return (handle & SHARDED_TAG) ? g_sharded.get(handle & ~SHARDED_TAG) : nullptr;
 }
 
 GMSM_EXPORT int gmsm_bases_register_sharded(int group, const uint64_t *points, size_t n, const int *devices, int n_devices,
@@ -873,39 +862,24 @@ GMSM_EXPORT int gmsm_bases_register_sharded(int group, const uint64_t *points, s
     else if (int rc0 = shard_devices(sb->devices)) return rc0;
     const int ndev = gmsm_device_count();
     if (ndev <= 0) return fail(GMSM_ERR_DEVICE, "no usable HIP device; libgmsm has no CPU fallback");
-    if (sb->devices.empty())
-        for (int d = 0; d < ndev; ++d) sb->devices.push_back(d);
-    for (int d : sb->devices)
-        if (d < 0 || d >= ndev)
-            return fail(GMSM_ERR_DEVICE, "gmsm_bases_register_sharded: device " + std::to_string(d) + " does not exist (" +
-                                             std::to_string(ndev) + " visible)");
+    if (sb->devices.empty()) every_device(ndev, sb->devices);
+    if (int rc = devices_exist("gmsm_bases_register_sharded", sb->devices.data(), sb->devices.size(), ndev)) return rc;
     // one upload per distinct device, all of them at once (every device has its own PCIe link)
     std::vector<int> distinct;
     for (int d : sb->devices)
         if (std::find(distinct.begin(), distinct.end(), d) == distinct.end()) distinct.push_back(d);
     std::vector<uint64_t> handles(distinct.size(), 0);
-    std::vector<int> rcs(distinct.size(), GMSM_OK);
-    std::vector<std::string> errs(distinct.size());
-    std::vector<std::thread> th;
+    const Failure bad = on_threads(distinct.size(), [&](size_t i) {
+        g_device = distinct[i];  // the worker's own device: gmsm_bases_register uploads to the calling thread's
+        return gmsm_bases_register(group, points, nullptr, n, &handles[i]);
+    });
     for (size_t i = 0; i < distinct.size(); ++i)
-        th.emplace_back([&, i] {
-            g_device = distinct[i];  // the worker's own device: gmsm_bases_register uploads to the calling thread's
-            rcs[i] = gmsm_bases_register(group, points, nullptr, n, &handles[i]);
-            if (rcs[i]) errs[i] = gmsm_last_error();
-        });
-    for (auto &t : th) t.join();
-    int rc = GMSM_OK;
-    for (size_t i = 0; i < distinct.size(); ++i) {
-        if (rcs[i] != GMSM_OK && rc == GMSM_OK) rc = fail(rcs[i], "device " + std::to_string(distinct[i]) + ": " + errs[i]);
         if (handles[i]) {
-            sb->replicas[distinct[i]] = lookup_bases(handles[i]);
+            sb->replicas[distinct[i]] = g_bases.get(handles[i]);
             (void)gmsm_bases_release(handles[i]);  // the per-device table entry goes; `replicas` keeps the bases alive
         }
-    }
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_bases_mu);
-    g_sharded.push_back(sb);
-    *out_handle = SHARDED_TAG | (uint64_t)g_sharded.size();
+    if (bad.rc) return fail(bad.rc, "device " + std::to_string(distinct[bad.index]) + ": " + bad.err);
+    *out_handle = SHARDED_TAG | g_sharded.add(sb);
     return GMSM_OK;
 }
 
@@ -936,24 +910,12 @@ GMSM_EXPORT int gmsm_bases_precompute(uint64_t handle, unsigned c) {
     if (handle & SHARDED_TAG) {
         std::shared_ptr<ShardedBases> sb = lookup_sharded(handle);
         if (!sb) return fail(GMSM_ERR_ARG, "unknown bases handle");
-        std::vector<std::thread> th;
-        std::vector<int> rcs(sb->replicas.size(), GMSM_OK);
-        std::vector<std::string> errs(sb->replicas.size());
-        size_t i = 0;
-        for (auto &kv : sb->replicas) {
-            BasesRef rb = kv.second;
-            th.emplace_back([&, rb, i] {
-                rcs[i] = precompute_on(rb, c);
-                if (rcs[i]) errs[i] = gmsm_last_error();
-            });
-            ++i;
-        }
-        for (auto &t : th) t.join();
-        for (size_t k = 0; k < rcs.size(); ++k)
-            if (rcs[k]) return fail(rcs[k], errs[k]);
-        return GMSM_OK;
+        std::vector<BasesRef> replicas;
+        for (auto &kv : sb->replicas) replicas.push_back(kv.second);
+        const Failure bad = on_threads(replicas.size(), [&](size_t i) { return precompute_on(replicas[i], c); });
+        return bad.rc ? fail(bad.rc, bad.err) : GMSM_OK;
     }
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     return precompute_on(rb, c);
 }
@@ -968,24 +930,16 @@ GMSM_EXPORT unsigned gmsm_bases_table_bits(uint64_t handle) {
         if (!sb || sb->replicas.empty()) return 0;
         return sb->replicas.begin()->second->tab_c.load();
     }
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     return rb ? rb->tab_c.load() : 0;
 }
 
 GMSM_EXPORT int gmsm_bases_release(uint64_t handle) {
     BasesRef rb;
     std::shared_ptr<ShardedBases> sb;
-    {
-        std::lock_guard<std::mutex> lk(g_bases_mu);
-        if (handle & SHARDED_TAG) {
-            const uint64_t i = handle & ~SHARDED_TAG;
-            if (i == 0 || i > g_sharded.size() || !g_sharded[i - 1]) return fail(GMSM_ERR_ARG, "unknown bases handle");
-            sb.swap(g_sharded[i - 1]);
-        } else {
-            if (handle == 0 || handle > g_bases.size() || !g_bases[handle - 1]) return fail(GMSM_ERR_ARG, "unknown bases handle");
-            rb.swap(g_bases[handle - 1]);
-        }
-    }
+    if (handle & SHARDED_TAG) sb = g_sharded.take(handle & ~SHARDED_TAG);
+    else rb = g_bases.take(handle);
+    if (!rb && !sb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     // Calls and tickets that are still using the bases hold their own references; the memory goes with the last one. A
     // reference that an enqueue-only call parked on an idle workspace would otherwise live until that workspace is leased
     // again: drop it here once its work has finished (outside the context lock - the destructor synchronises the device).
@@ -1012,15 +966,13 @@ GMSM_EXPORT int gmsm_bases_release(uint64_t handle) {
 
 static int multiexp_bases_impl(uint64_t handle, const uint64_t *scalars, const void *d_scalars, size_t n, int nb_tasks,
                                void *hip_stream, uint64_t *out_jac) {
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
     if (n > rb->n) return fail(GMSM_ERR_LEN, "len(points) != len(scalars)");  // more scalars than registered bases
     if (nb_tasks > 1024) return fail(GMSM_ERR_CONFIG, "invalid config: config.NbTasks > 1024");
     Context *ctx;
-    int rc = get_context_for(rb->device, &ctx);  // the bases decide the device, not the calling thread
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = enter_on(rb->device, &ctx)) return rc;  // the bases decide the device, not the calling thread
     if (scalars && n) return vt->multiexp_bases_host(*ctx, scalars, n, out_jac, rb.get());
     return vt->multiexp_device(*ctx, nullptr, d_scalars, n, (hipStream_t)hip_stream, out_jac, rb.get());
 }
@@ -1058,15 +1010,14 @@ GMSM_EXPORT int gmsm_multiexp_bases_device(uint64_t handle, const void *d_scalar
 // ticket = device << 40 | generation << 8 | (slot + 1)
 GMSM_EXPORT int gmsm_multiexp_bases_submit(uint64_t handle, const void *d_scalars, size_t n_scalars, void *hip_stream,
                                            uint64_t *out_ticket) {
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     if (!out_ticket) return fail(GMSM_ERR_ARG, "out_ticket is null");
     const GroupVTable *vt = vtable(rb->group);
     if (n_scalars > rb->n) return fail(GMSM_ERR_LEN, "len(points) != len(scalars)");
     Context *ctx;
-    int rc = get_context_for(rb->device, &ctx);
+    int rc = enter_on(rb->device, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     int why = 0;
     Lease lease(*ctx, /*wait=*/false, /*for_ticket=*/true, &why);
     Workspace *ws = lease.w;
@@ -1107,22 +1058,15 @@ GMSM_EXPORT int gmsm_multiexp_bases_batch(uint64_t handle, const uint64_t *scala
         if (n && !scalars) return fail(GMSM_ERR_ARG, "gmsm_multiexp_bases_batch: a sharded handle takes host scalars");
         const GroupVTable *vts = vtable(sb->group);
         const size_t G = std::min<size_t>(sb->devices.size(), k), jl = vts->jac_bytes / 8, sl = vts->scalar_bytes / 8 * n;
-        std::vector<int> rcs(G, GMSM_OK);
-        std::vector<std::string> errs(G);
-        std::vector<std::thread> th;
-        for (size_t r = 0; r < G; ++r)
-            th.emplace_back([&, r] {
-                const size_t lo = r * k / G, hi = (r + 1) * k / G;
-                const BasesRef &rb = sb->replicas.at(sb->devices[r]);
-                rcs[r] = multiexp_bases_batch_on(rb, scalars ? scalars + lo * sl : nullptr, nullptr, n, hi - lo, nullptr, out_jac + lo * jl);
-                if (rcs[r]) errs[r] = gmsm_last_error();
-            });
-        for (auto &t : th) t.join();
-        for (size_t r = 0; r < G; ++r)
-            if (rcs[r]) return fail(rcs[r], "rank " + std::to_string(r) + " (device " + std::to_string(sb->devices[r]) + "): " + errs[r]);
+        const Failure bad = on_threads(G, [&](size_t r) {
+            const size_t lo = r * k / G, hi = (r + 1) * k / G;
+            const BasesRef &rb = sb->replicas.at(sb->devices[r]);
+            return multiexp_bases_batch_on(rb, scalars ? scalars + lo * sl : nullptr, nullptr, n, hi - lo, nullptr, out_jac + lo * jl);
+        });
+        if (bad.rc) return fail(bad.rc, "rank " + std::to_string(bad.index) + " (device " + std::to_string(sb->devices[bad.index]) + "): " + bad.err);
         return GMSM_OK;
     }
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     if (n > rb->n) return fail(GMSM_ERR_LEN, "len(points) != len(scalars)");
     if (k == 0) return GMSM_OK;
@@ -1135,9 +1079,8 @@ static int multiexp_bases_batch_on(const BasesRef &rb, const uint64_t *scalars, 
                                    void *hip_stream, uint64_t *out_jac) {
     const GroupVTable *vt = vtable(rb->group);
     Context *ctx;
-    int rc = get_context_for(rb->device, &ctx);
+    int rc = enter_on(rb->device, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     const size_t jl = vt->jac_bytes / 8, sb = vt->scalar_bytes * n;
     if (n == 0) {
         for (size_t i = 0; i < k; ++i)
@@ -1153,7 +1096,7 @@ static int multiexp_bases_batch_on(const BasesRef &rb, const uint64_t *scalars, 
     while (rc == GMSM_OK && collected < k) {
         while (rc == GMSM_OK && submitted < k && submitted - collected < nws) {
             Workspace &ws = *w[submitted % nws];
-            const void *dsc;
+            const void *dsc;  // written out, not stage_input: a failed copy must end the loop, and has a text of its own
             if (scalars) {
                 if ((rc = ws.h2d_scalars.ensure(sb))) break;
                 hipError_t e = hipMemcpyAsync(ws.h2d_scalars.ptr, (const char *)scalars + submitted * sb, sb,
@@ -1209,14 +1152,7 @@ GMSM_EXPORT int gmsm_multiexp_collect(uint64_t ticket, uint64_t *out_jac) {
 
 // ------------------------------------------------------------------ fr/fft
 using FftRef = std::shared_ptr<FftDomain>;
-static std::mutex g_fft_mu;
-static std::vector<FftRef> g_fft;  // handle = index + 1
-
-static FftRef lookup_fft(uint64_t handle) {
-    std::lock_guard<std::mutex> lk(g_fft_mu);
-    if (handle == 0 || handle > g_fft.size()) return nullptr;
-    return g_fft[handle - 1];
-}
+static HandleTable<FftDomain> g_fft;
 
 GMSM_EXPORT int gmsm_fft_domain_new(int group, uint64_t m, uint64_t *out_handle) {
     VT_OR_FAIL(group);
@@ -1224,32 +1160,26 @@ GMSM_EXPORT int gmsm_fft_domain_new(int group, uint64_t m, uint64_t *out_handle)
     unsigned log2n = 0;  // ecc.NextPowerOfTwo(m)
     while (log2n < 63 && ((uint64_t)1 << log2n) < m) ++log2n;
     Context *ctx;
-    int rc = get_context(&ctx);
+    int rc = enter(&ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     FftRef d = std::make_shared<FftDomain>();
     d->group = group;
     d->device = ctx->device;
     if ((rc = vt->fft_domain_new(*ctx, lease.w->stream, log2n, d.get()))) return rc;
-    std::lock_guard<std::mutex> lk(g_fft_mu);
-    g_fft.push_back(d);
-    *out_handle = g_fft.size();
+    *out_handle = g_fft.add(d);
     return GMSM_OK;
 }
 
 GMSM_EXPORT int gmsm_fft_domain_release(uint64_t handle) {
-    FftRef d;
-    std::lock_guard<std::mutex> lk(g_fft_mu);
-    if (handle == 0 || handle > g_fft.size() || !g_fft[handle - 1]) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
-    d.swap(g_fft[handle - 1]);
+    if (!g_fft.take(handle)) return fail(GMSM_ERR_ARG, "unknown fft domain handle");  // the tables go with the last reference
     return GMSM_OK;
 }
 
 GMSM_EXPORT int gmsm_fft_domain_info(uint64_t handle, uint64_t *cardinality, uint64_t *generator, uint64_t *generator_inv,
                                      uint64_t *cardinality_inv, uint64_t *fr_multiplicative_gen,
                                      uint64_t *fr_multiplicative_gen_inv) {
-    FftRef d = lookup_fft(handle);
+    FftRef d = g_fft.get(handle);
     if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
     if (cardinality) *cardinality = (uint64_t)1 << d->log2n;
     auto put = [](uint64_t *dst, const std::vector<uint64_t> &src) {
@@ -1265,32 +1195,27 @@ GMSM_EXPORT int gmsm_fft_domain_info(uint64_t handle, uint64_t *cardinality, uin
 
 GMSM_EXPORT int gmsm_fft(uint64_t handle, uint64_t *a, void *d_a, size_t n, int inverse, int decimation, int on_coset,
                          void *hip_stream) {
-    FftRef d = lookup_fft(handle);
+    FftRef d = g_fft.get(handle);
     if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
     const GroupVTable *vt = vtable(d->group);
     if (n != ((size_t)1 << d->log2n)) return fail(GMSM_ERR_LEN, "len(a) must equal the domain's cardinality");
     if ((a == nullptr) == (d_a == nullptr)) return fail(GMSM_ERR_ARG, "gmsm_fft: give exactly one of a (host) / d_a (device)");
     if (decimation != 0 && decimation != 1) return fail(GMSM_ERR_ARG, "gmsm_fft: decimation must be 0 (DIT) or 1 (DIF)");
     Context *ctx;
-    int rc = get_context_for(d->device, &ctx);
+    int rc = enter_on(d->device, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     Workspace &ws = *lease.w;
     const size_t bytes = n * vt->scalar_bytes;
-    void *dev = d_a;
-    if (a) {
-        if ((rc = ws.h2d_scalars.ensure(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws.h2d_scalars.ptr, a, bytes, hipMemcpyHostToDevice, ws.stream));
-        dev = ws.h2d_scalars.ptr;
-    } else {
+    if (!a) {
         hipPointerAttribute_t attr;  // a vector on another GPU would fault (or read garbage) under this domain's tables
         if (hipPointerGetAttributes(&attr, d_a) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != d->device) {
             (void)hipGetLastError();
             return fail(GMSM_ERR_ARG, "gmsm_fft: d_a is not device memory of the domain's device");
         }
-        if ((rc = order_after(ws, (hipStream_t)hip_stream))) return rc;
     }
+    void *dev;
+    if ((rc = stage_input(ws, ws.h2d_scalars, a, d_a, bytes, {After::STREAM, (hipStream_t)hip_stream}, &dev))) return rc;
     {
         std::lock_guard<std::mutex> lk(d->mu);
         rc = vt->fft_run(ws.stream, d.get(), dev, inverse != 0, decimation == 1, on_coset != 0);
@@ -1306,20 +1231,13 @@ GMSM_EXPORT int gmsm_fft_bit_reverse(int group, uint64_t *a, void *d_a, size_t n
     if ((a == nullptr) == (d_a == nullptr) && n) return fail(GMSM_ERR_ARG, "gmsm_fft_bit_reverse: give exactly one of a / d_a");
     if (n == 0) return GMSM_OK;
     Context *ctx;
-    int rc = get_context_of_pointer(d_a, &ctx);
+    int rc = enter_owner(d_a, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     GMSM_LEASE_OR_FAIL(lease, *ctx);
     Workspace &ws = *lease.w;
     const size_t bytes = n * vt->scalar_bytes;
-    void *dev = d_a;
-    if (a) {
-        if ((rc = ws.h2d_scalars.ensure(bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws.h2d_scalars.ptr, a, bytes, hipMemcpyHostToDevice, ws.stream));
-        dev = ws.h2d_scalars.ptr;
-    } else if ((rc = order_after(ws, (hipStream_t)hip_stream))) {
-        return rc;
-    }
+    void *dev;
+    if ((rc = stage_input(ws, ws.h2d_scalars, a, d_a, bytes, {After::STREAM, (hipStream_t)hip_stream}, &dev))) return rc;
     if ((rc = vt->fft_bit_reverse(ws.stream, dev, n))) return rc;
     if (a) HIP_TRY(hipMemcpyAsync(a, dev, bytes, hipMemcpyDeviceToHost, ws.stream));
     HIP_TRY(hipStreamSynchronize(ws.stream));
@@ -1352,9 +1270,8 @@ GMSM_EXPORT int gmsm_poly_eval(int group, const uint64_t *polys, const void *d_p
     for (size_t i = 0; i < k; ++i)
         if (lens[i] == 0) return fail(GMSM_ERR_ARG, "gmsm_poly_eval: polynomial " + std::to_string(i) + " is empty (eval reads p[len(p)-1])");
     Context *ctx;
-    int rc = get_context_of_pointer(d_polys, &ctx);
+    int rc = enter_owner(d_polys, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = check_device_vector("gmsm_poly_eval", "d_polys", d_polys, ctx->device))) return rc;
     return vt->poly_eval(*ctx, polys, d_polys, lens, k, point, (hipStream_t)hip_stream, out_values);
 }
@@ -1371,9 +1288,8 @@ GMSM_EXPORT int gmsm_poly_div_x_minus_a(int group, const uint64_t *poly, const v
     if ((poly && (poly == out_h || poly == out_value)) || (d_poly && d_poly == d_out_h) || (out_h && out_h == out_value))
         return fail(GMSM_ERR_ARG, std::string(E) + ": an output aliases the input or another output (inputs are never modified)");
     Context *ctx;
-    int rc = get_context_of_pointer(d_poly ? d_poly : d_out_h, &ctx);
+    int rc = enter_owner(d_poly ? d_poly : d_out_h, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = check_device_vector(E, "d_poly", d_poly, ctx->device)) || (rc = check_device_vector(E, "d_out_h", n > 1 ? d_out_h : nullptr, ctx->device)))
         return rc;
     return vt->poly_div(*ctx, poly, d_poly, n, point, (hipStream_t)hip_stream, n > 1 ? out_h : nullptr, n > 1 ? d_out_h : nullptr, out_value);
@@ -1394,14 +1310,13 @@ static int kzg_open_impl(const char *E, uint64_t handle, const uint64_t *polys, 
     if (out_claimed && (out_claimed == out_h_jac || out_claimed == polys))
         return fail(GMSM_ERR_ARG, std::string(E) + ": out_claimed aliases another argument");
     if (polys && polys == out_h_jac) return fail(GMSM_ERR_ARG, std::string(E) + ": out_h_jac aliases polys (inputs are never modified)");
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     if (maxlen > rb->n) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);
     const GroupVTable *vt = vtable(rb->group);
     Context *ctx;
-    int rc = get_context_for(rb->device, &ctx);  // the bases decide the device
+    int rc = enter_on(rb->device, &ctx);  // the bases decide the device
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
     return vt->kzg_open(*ctx, polys, d_polys, lens, k, point, k > 1 ? gamma : nullptr, (hipStream_t)hip_stream, out_claimed, out_h_jac,
                         rb.get());
@@ -1439,15 +1354,14 @@ static int open_nonempty(const char *E, bool packed, const size_t *lens, const s
 static int open_check(const char *E, uint64_t handle, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes,
                       size_t k, const uint64_t *points, const size_t *npoints, BasesRef *rb_out, const GroupVTable **vt_out, Context **ctx_out) {
     if ((polys == nullptr) == (d_polys == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of polys (host) / d_polys (device)");
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
     if (!vt->open_w) return fail(GMSM_ERR_ARG, pack_sizes ? ERR_FFLONK_G1 : ERR_SHPLONK_G1);
     int rc = vt->open_check(E, lens, pack_sizes, k, points, npoints, true, rb->n);
     if (rc) return rc;
     Context *ctx;
-    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
-    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = enter_on(rb->device, &ctx))) return rc;  // the bases decide the device
     if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
     *rb_out = rb, *vt_out = vt, *ctx_out = ctx;
     return GMSM_OK;
@@ -1522,8 +1436,7 @@ GMSM_EXPORT int gmsm_fflonk_fold(int group, const uint64_t *polys, const void *d
     int rc = fflonk_pack_args(E, polys, d_polys, lens, npolys);
     if (rc || (rc = vt->open_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
     Context *ctx;
-    if ((rc = get_context_of_pointer(d_polys ? d_polys : d_out, &ctx))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = enter_owner(d_polys ? d_polys : d_out, &ctx))) return rc;
     if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
     return vt->fflonk_fold(*ctx, polys, d_polys, lens, npolys, (hipStream_t)hip_stream, out, d_out, nullptr, nullptr);
 }
@@ -1536,7 +1449,7 @@ GMSM_EXPORT int gmsm_fflonk_fold_commit(uint64_t handle, const uint64_t *polys, 
         return fail(GMSM_ERR_ARG, std::string(E) + ": an output aliases the input (inputs are never modified)");
     int rc = fflonk_pack_args(E, polys, d_polys, lens, npolys);
     if (rc) return rc;
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
     if (!vt->open_w) return fail(GMSM_ERR_ARG, ERR_FFLONK_G1);
@@ -1546,8 +1459,7 @@ GMSM_EXPORT int gmsm_fflonk_fold_commit(uint64_t handle, const uint64_t *polys, 
     for (size_t j = 0; j < npolys; ++j) n = std::max(n, lens[j]);
     if (t * n > rb->n) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);  // Commit's size check (kzg.go:159-162) over the folded length
     Context *ctx;
-    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
-    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = enter_on(rb->device, &ctx))) return rc;  // the bases decide the device
     if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device)) || (rc = check_device_vector(E, "d_out_folded", d_out_folded, ctx->device)))
         return rc;
     return vt->fflonk_fold(*ctx, polys, d_polys, lens, npolys, (hipStream_t)hip_stream, nullptr, d_out_folded, rb.get(), out_jac);
@@ -1627,8 +1539,7 @@ GMSM_EXPORT int gmsm_to_lagrange_g1(int group, const uint64_t *coeffs, const voi
     if ((out_affine == nullptr) == (d_out_affine == nullptr))
         return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_affine (host) / d_out_affine (device)");
     Context *ctx;
-    if ((rc = get_context_of_pointer(d_coeffs ? d_coeffs : d_out_affine, &ctx))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = enter_owner(d_coeffs ? d_coeffs : d_out_affine, &ctx))) return rc;
     if ((rc = check_device_vector(E, "d_coeffs", d_coeffs, ctx->device)) || (rc = check_device_vector(E, "d_out_affine", d_out_affine, ctx->device)))
         return rc;
     return vt->to_lagrange(*ctx, coeffs, d_coeffs, nullptr, log2n, (hipStream_t)hip_stream, out_affine, d_out_affine, nullptr);
@@ -1636,7 +1547,7 @@ GMSM_EXPORT int gmsm_to_lagrange_g1(int group, const uint64_t *coeffs, const voi
 
 GMSM_EXPORT int gmsm_bases_to_lagrange(uint64_t handle, size_t n, uint64_t *out_handle) {
     if (!out_handle) return fail(GMSM_ERR_ARG, "gmsm_bases_to_lagrange: out_handle is null");
-    BasesRef rb = lookup_bases(handle);
+    BasesRef rb = g_bases.get(handle);
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
     if (!vt->to_lagrange) return fail(GMSM_ERR_ARG, ERR_G1_ONLY);
@@ -1645,15 +1556,12 @@ GMSM_EXPORT int gmsm_bases_to_lagrange(uint64_t handle, size_t n, uint64_t *out_
     if (rc) return rc;
     if (n > rb->n) return fail(GMSM_ERR_ARG, "gmsm_bases_to_lagrange: n is larger than the registered bases");
     Context *ctx;
-    if ((rc = get_context_for(rb->device, &ctx))) return rc;  // the bases decide the device
-    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = enter_on(rb->device, &ctx))) return rc;  // the bases decide the device
     BasesRef out = std::make_shared<ResidentBases>();
     out->group = rb->group;
     out->device = ctx->device;
     if ((rc = vt->to_lagrange(*ctx, nullptr, nullptr, rb.get(), log2n, nullptr, nullptr, nullptr, out.get()))) return rc;
-    std::lock_guard<std::mutex> lk(g_bases_mu);
-    g_bases.push_back(out);
-    *out_handle = g_bases.size();
+    *out_handle = g_bases.add(out);
     return GMSM_OK;
 }
 
@@ -1667,9 +1575,8 @@ static int scale_call(const char *E, const GroupVTable *vt, const uint64_t *poin
     if ((out_affine == nullptr) == (d_out_affine == nullptr))
         return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out_affine (host) / d_out_affine (device)");
     Context *ctx;
-    int rc = get_context_of_pointer(d_points ? d_points : d_out_affine ? d_out_affine : d_scalars, &ctx);
+    int rc = enter_owner(d_points ? d_points : d_out_affine ? d_out_affine : d_scalars, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = check_device_vector(E, "d_points", d_points, ctx->device)) || (rc = check_device_vector(E, "d_scalars", d_scalars, ctx->device)) ||
         (rc = check_device_vector(E, "d_out_affine", d_out_affine, ctx->device)))
         return rc;
@@ -1705,9 +1612,8 @@ GMSM_EXPORT int gmsm_linear_combinations(int group, const uint64_t *points, cons
     }
     if (ends[n_ends - 1] != n) return fail(GMSM_ERR_ARG, "lengths mismatch");
     Context *ctx;
-    int rc = get_context_of_pointer(d_points, &ctx);
+    int rc = enter_owner(d_points, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = check_device_vector(E, "d_points", d_points, ctx->device))) return rc;
     return vt->linear_combinations(*ctx, points, d_points, n, ends, n_ends, r, (hipStream_t)hip_stream, out_truncated_jac, out_shifted_jac);
 }
@@ -1718,9 +1624,8 @@ GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, co
     VT_OR_FAIL(group);
     if (!base_affine || (n && (!scalars || !out_affine))) return fail(GMSM_ERR_ARG, "gmsm_batch_scalar_mul: null argument");
     Context *ctx;
-    int rc = get_context(&ctx);
+    int rc = enter(&ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     return vt->batch_scalar_mul(*ctx, base_affine, scalars, nullptr, n, nullptr, out_affine, nullptr);
 }
 
@@ -1730,9 +1635,8 @@ GMSM_EXPORT int gmsm_batch_scalar_mul_device(int group, const uint64_t *base_aff
     if (!base_affine || (n && (!d_scalars || !d_out_affine)))
         return fail(GMSM_ERR_ARG, "gmsm_batch_scalar_mul_device: null argument");
     Context *ctx;
-    int rc = get_context_of_pointer(d_scalars, &ctx);
+    int rc = enter_owner(d_scalars, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     return vt->batch_scalar_mul(*ctx, base_affine, nullptr, d_scalars, n, (hipStream_t)hip_stream, nullptr, d_out_affine);
 }
 
@@ -1740,9 +1644,8 @@ GMSM_EXPORT int gmsm_batch_jac_to_affine(int group, const uint64_t *jac, size_t 
     VT_OR_FAIL(group);
     if (n && (!jac || !out_affine)) return fail(GMSM_ERR_ARG, "gmsm_batch_jac_to_affine: null argument");
     Context *ctx;
-    int rc = get_context(&ctx);
+    int rc = enter(&ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     return vt->batch_jac_to_affine(*ctx, jac, n, out_affine);
 }
 
@@ -1782,9 +1685,8 @@ GMSM_EXPORT int gmsm_window_sums_device(int group, const void *d_points, const v
     VT_OR_FAIL(group);
     if (c < 2 || c > 20) return fail(GMSM_ERR_ARG, "c out of range (2..20)");
     Context *ctx;
-    int rc = get_context_of_pointer(d_scalars, &ctx);
+    int rc = enter_owner(d_scalars, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     return vt->window_sums(*ctx, d_points, d_scalars, n, c, win_first, win_stride, (hipStream_t)hip_stream, out_xyzz, nullptr);
 }
 
@@ -1796,14 +1698,13 @@ GMSM_EXPORT int gmsm_window_sums_enqueue(int group, const void *d_points, uint64
     if (!d_out_xyzz) return fail(GMSM_ERR_ARG, "d_out_xyzz is null");
     BasesRef rb;
     if (bases_handle) {
-        rb = lookup_bases(bases_handle);
+        rb = g_bases.get(bases_handle);
         if (!rb || rb->group != group) return fail(GMSM_ERR_ARG, "unknown bases handle");
         if (n > rb->n) return fail(GMSM_ERR_LEN, "len(points) != len(scalars)");
     }
     Context *ctx;
-    int rc = rb ? get_context_for(rb->device, &ctx) : get_context_of_pointer(d_out_xyzz, &ctx);
+    int rc = rb ? enter_on(rb->device, &ctx) : enter_owner(d_out_xyzz, &ctx);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
     // hip_stream is used as given: NULL is the device's default (null) stream, which is what the consumer of d_out_xyzz
     // is ordered against when it runs there too - not the engine's private stream.
     return vt->window_sums_enqueue(*ctx, d_points, d_scalars, n, c, win_first, win_stride, (hipStream_t)hip_stream,
@@ -1917,13 +1818,8 @@ GMSM_EXPORT int gmsm_set_devices(const int *devices, int count) {
     std::vector<int> list;
     if (count > 0) {
         if (!devices) return fail(GMSM_ERR_ARG, "gmsm_set_devices: devices is null");
-        const int n = gmsm_device_count();
-        for (int i = 0; i < count; ++i) {
-            if (devices[i] < 0 || devices[i] >= n)
-                return fail(GMSM_ERR_DEVICE, "gmsm_set_devices: device " + std::to_string(devices[i]) + " does not exist (" +
-                                                 std::to_string(n) + " visible)");
-            list.push_back(devices[i]);
-        }
+        if (int rc = devices_exist("gmsm_set_devices", devices, (size_t)count, gmsm_device_count())) return rc;
+        list.assign(devices, devices + count);
     }
     std::lock_guard<std::mutex> lk(g_devices_mu);
     g_devices = list;
@@ -1946,72 +1842,54 @@ GMSM_EXPORT int gmsm_get_devices(int *out_devices, int max_devices) {
 }
 
 // ------------------------------------------------------------------ switches and lifecycle
+// One row per key, read by both entries: a key cannot be settable and unreadable. `accepts` null: every value.
+struct OptionRow {
+    int key;
+    std::atomic<unsigned> Options::*member;
+    bool (*accepts)(unsigned value);
+    const char *refusal;
+    bool as_flag = false;  // stored as value != 0
+};
+static const OptionRow OPTION_ROWS[] = {
+    {GMSM_OPT_WINDOW_BITS, &Options::window_bits, [](unsigned v) { return v == 0 || (v >= 2 && v <= 20); },
+     "GMSM_OPT_WINDOW_BITS: 0 (the measured table) or 2..20"},
+    {GMSM_OPT_TABLES, &Options::tables, [](unsigned v) { return v <= 2; }, "GMSM_OPT_TABLES: 0 never, 1 the measured call sizes, 2 every call size"},
+    {GMSM_OPT_MAX_RUN, &Options::max_run, nullptr, nullptr},
+    {GMSM_OPT_HOST_RANGES, &Options::host_ranges, nullptr, nullptr},
+    {GMSM_OPT_FIXED_BASE_BITS, &Options::fixed_base_bits, [](unsigned v) { return v == 0 || (v >= 2 && v <= 14); },
+     "GMSM_OPT_FIXED_BASE_BITS: 0 (by batch size) or 2..14"},
+    {GMSM_OPT_SMALL_BITS, &Options::small_bits, [](unsigned v) { return v <= 7; },
+     "GMSM_OPT_SMALL_BITS: 0 (on, width by size), 1 (off) or 2..7 (on, forced width)"},
+    {GMSM_OPT_SMALL_MAX, &Options::small_max, nullptr, nullptr},
+    {GMSM_OPT_SPLIT, &Options::split, nullptr, nullptr, true},
+    {GMSM_OPT_GLV, &Options::glv, [](unsigned v) { return v <= 2; }, "GMSM_OPT_GLV: 0 never, 1 where measured ahead, 2 every unregistered call"},
+    {GMSM_OPT_SMALL_QUAD, &Options::small_quad, [](unsigned v) { return v <= 2; }, "GMSM_OPT_SMALL_QUAD: 0 by call size, 1 never, 2 always"},
+    {GMSM_OPT_POLY_LANE_BITS, &Options::poly_lane_bits, [](unsigned v) { return v <= 6; },
+     "GMSM_OPT_POLY_LANE_BITS: 0 (lane width by length) or 1..6 (lanes of 2^(k-1) coefficients)"},
+    {GMSM_OPT_REDUCE_SHAPE, &Options::reduce_shape,
+     [](unsigned v) { return !(v > 255 || (v & 15u) > 8 || ((v >> 4) & 3u) == 1 || ((v >> 6) & 3u) == 3); },
+     "GMSM_OPT_REDUCE_SHAPE: 0 (the cost model) or log2L (0, 1..8) | levels (0, 2, 3) << 4 | combine kernel (0, 1, 2) << 6"},
+    {GMSM_OPT_SPIN_WAIT_US, &Options::spin_wait_us, [](unsigned v) { return v <= 1000000; }, "GMSM_OPT_SPIN_WAIT_US: at most 1000000"},
+};
+static const OptionRow *option_row(int key) {
+    for (const OptionRow &r : OPTION_ROWS)
+        if (r.key == key) return &r;
+    return nullptr;
+}
+
 GMSM_EXPORT int gmsm_set_option(int key, unsigned value) {
     Options &o = options();
-    switch (key) {
-        case GMSM_OPT_WINDOW_BITS:
-            if (value != 0 && (value < 2 || value > 20)) return fail(GMSM_ERR_ARG, "GMSM_OPT_WINDOW_BITS: 0 (the measured table) or 2..20");
-            o.window_bits.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_TABLES:
-            if (value > 2) return fail(GMSM_ERR_ARG, "GMSM_OPT_TABLES: 0 never, 1 the measured call sizes, 2 every call size");
-            o.tables.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_MAX_RUN: o.max_run.store(value); return GMSM_OK;
-        case GMSM_OPT_HOST_RANGES: o.host_ranges.store(value); return GMSM_OK;
-        case GMSM_OPT_FIXED_BASE_BITS:
-            if (value != 0 && (value < 2 || value > 14)) return fail(GMSM_ERR_ARG, "GMSM_OPT_FIXED_BASE_BITS: 0 (by batch size) or 2..14");
-            o.fixed_base_bits.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_SMALL_BITS:
-            if (value > 7) return fail(GMSM_ERR_ARG, "GMSM_OPT_SMALL_BITS: 0 (on, width by size), 1 (off) or 2..7 (on, forced width)");
-            o.small_bits.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_SMALL_MAX: o.small_max.store(value); return GMSM_OK;
-        case GMSM_OPT_SPLIT: o.split.store(value ? 1 : 0); return GMSM_OK;
-        case GMSM_OPT_GLV:
-            if (value > 2) return fail(GMSM_ERR_ARG, "GMSM_OPT_GLV: 0 never, 1 where measured ahead, 2 every unregistered call");
-            o.glv.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_SMALL_QUAD:
-            if (value > 2) return fail(GMSM_ERR_ARG, "GMSM_OPT_SMALL_QUAD: 0 by call size, 1 never, 2 always");
-            o.small_quad.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_POLY_LANE_BITS:
-            if (value > 6) return fail(GMSM_ERR_ARG, "GMSM_OPT_POLY_LANE_BITS: 0 (lane width by length) or 1..6 (lanes of 2^(k-1) coefficients)");
-            o.poly_lane_bits.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_REDUCE_SHAPE:
-            if (value > 255 || (value & 15u) > 8 || ((value >> 4) & 3u) == 1 || ((value >> 6) & 3u) == 3)
-                return fail(GMSM_ERR_ARG, "GMSM_OPT_REDUCE_SHAPE: 0 (the cost model) or log2L (0, 1..8) | levels (0, 2, 3) << 4 | combine kernel (0, 1, 2) << 6");
-            o.reduce_shape.store(value);
-            return GMSM_OK;
-        case GMSM_OPT_SPIN_WAIT_US:
-            if (value > 1000000) return fail(GMSM_ERR_ARG, "GMSM_OPT_SPIN_WAIT_US: at most 1000000");
-            o.spin_wait_us.store(value);
-            return GMSM_OK;
-        default: return fail(GMSM_ERR_ARG, "gmsm_set_option: unknown key");
-    }
+    const OptionRow *r = option_row(key);
+    if (!r) return fail(GMSM_ERR_ARG, "gmsm_set_option: unknown key");
+    if (r->accepts && !r->accepts(value)) return fail(GMSM_ERR_ARG, r->refusal);
+    (o.*r->member).store(r->as_flag ? (value ? 1 : 0) : value);
+    return GMSM_OK;
 }
 
 GMSM_EXPORT unsigned gmsm_get_option(int key) {
     Options &o = options();
-    switch (key) {
-        case GMSM_OPT_WINDOW_BITS: return o.window_bits.load();
-        case GMSM_OPT_TABLES: return o.tables.load();
-        case GMSM_OPT_MAX_RUN: return o.max_run.load();
-        case GMSM_OPT_HOST_RANGES: return o.host_ranges.load();
-        case GMSM_OPT_FIXED_BASE_BITS: return o.fixed_base_bits.load();
-        case GMSM_OPT_SPIN_WAIT_US: return o.spin_wait_us.load();
-        case GMSM_OPT_SMALL_BITS: return o.small_bits.load();
-        case GMSM_OPT_SMALL_MAX: return o.small_max.load();
-        case GMSM_OPT_SPLIT: return o.split.load();
-        case GMSM_OPT_GLV: return o.glv.load();
-        case GMSM_OPT_SMALL_QUAD: return o.small_quad.load();
-        case GMSM_OPT_POLY_LANE_BITS: return o.poly_lane_bits.load();
-        case GMSM_OPT_REDUCE_SHAPE: return o.reduce_shape.load();
-        default: return 0;
-    }
+    const OptionRow *r = option_row(key);
+    return r ? (o.*r->member).load() : 0;
 }
 
 // Scratch of the idle workspaces back to the device (the reference's buffers are per call and garbage-collected,
@@ -2078,20 +1956,10 @@ GMSM_EXPORT int gmsm_shutdown(void) {
         }
     }
     {
-        // The handle tables keep their length (a handle is index + 1: an old handle must stay unknown, not come to name
-        // a later registration); the memory goes with the last reference, at the end of this block.
-        std::vector<BasesRef> bases;
-        std::vector<std::shared_ptr<ShardedBases>> sharded;
-        {
-            std::lock_guard<std::mutex> lk(g_bases_mu);
-            for (auto &b : g_bases) bases.push_back(std::move(b)), b = nullptr;
-            for (auto &b : g_sharded) sharded.push_back(std::move(b)), b = nullptr;
-        }
-        std::vector<FftRef> ffts;
-        {
-            std::lock_guard<std::mutex> lk(g_fft_mu);
-            for (auto &d : g_fft) ffts.push_back(std::move(d)), d = nullptr;
-        }
+        // the memory goes with the last reference, at the end of this block (outside the tables' locks)
+        const auto bases = g_bases.drain();
+        const auto sharded = g_sharded.drain();
+        const auto ffts = g_fft.drain();
     }
     int prev = 0;
     (void)hipGetDevice(&prev);

@@ -87,12 +87,8 @@ struct VTableOf {
         Workspace &ws = *lease.w;
         int rc = order_after(ws, caller_stream);
         if (rc) return rc;
-        const void *dsc = d_scalars;
-        if (scalars && n) {
-            if ((rc = ws.h2d_scalars.ensure(n * G::SCALAR_BYTES))) return rc;
-            HIP_TRY(hipMemcpyAsync(ws.h2d_scalars.ptr, scalars, n * G::SCALAR_BYTES, hipMemcpyHostToDevice, ws.stream));
-            dsc = ws.h2d_scalars.ptr;
-        }
+        const void *dsc;  // (the caller's stream has been ordered above, whichever side the scalars are on)
+        if ((rc = stage_input(ws, ws.h2d_scalars, scalars, d_scalars, n * G::SCALAR_BYTES, {After::NOTHING}, &dsc))) return rc;
         void *dres = d_out;
         if (out && n) {
             if ((rc = ws.parted.ensure(n * G::AFF_BYTES))) return rc;
@@ -222,16 +218,10 @@ struct VTableOf {
     // the k polynomials on the device: host ones are staged in ws.h2d_scalars, device ones are read where they are, after
     // the work queued on the caller's stream
     static int poly_input(Workspace &ws, const uint64_t *polys, const void *d_polys, size_t total, hipStream_t caller, const Fr **out) {
-        int rc;
-        if (polys) {
-            if ((rc = ws.h2d_scalars.ensure(total * sizeof(Fr)))) return rc;
-            HIP_TRY(hipMemcpyAsync(ws.h2d_scalars.ptr, polys, total * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
-            *out = (const Fr *)ws.h2d_scalars.ptr;
-            return GMSM_OK;
-        }
-        if ((rc = order_after(ws, caller))) return rc;
-        *out = (const Fr *)d_polys;
-        return GMSM_OK;
+        const void *in;
+        int rc = stage_input(ws, ws.h2d_scalars, polys, d_polys, total * sizeof(Fr), {After::STREAM, caller}, &in);
+        *out = (const Fr *)in;
+        return rc;
     }
     static size_t word_slots(size_t words) { return (words * 8 + sizeof(Fr) - 1) / sizeof(Fr); }  // Fr-sized slots that hold 64-bit words
     static size_t poly_scratch(const size_t *lens, size_t k, unsigned lanes) {
@@ -415,29 +405,15 @@ struct VTableOf {
         memcpy(out_jac, &j, sizeof j);
         return GMSM_OK;
     }
-    static constexpr decltype(GroupVTable::open_w) open_w_entry() {
-        if constexpr (IS_G1) return &open_w;
-        else return nullptr;
-    }
-    static constexpr decltype(GroupVTable::open_wprime) open_wprime_entry() {
-        if constexpr (IS_G1) return &open_wprime;
-        else return nullptr;
-    }
     // ---- ToLagrangeG1 (gmsm_group_fft.h)
     static int to_lagrange(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
                            hipStream_t caller, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases) {
         GMSM_LEASE_OR_FAIL(lease, ctx);
         Workspace &ws = *lease.w;
         const size_t n = (size_t)1 << log2n, bytes = n * G::AFF_BYTES;
-        int rc;
-        const void *src = d_coeffs;
-        if (coeffs) {
-            if ((rc = ws.h2d_points.ensure(bytes))) return rc;
-            HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, coeffs, bytes, hipMemcpyHostToDevice, ws.stream));
-            src = ws.h2d_points.ptr;
-        } else if (from) {
-            src = from->upoints.ptr;
-        }
+        const void *src;  // host coefficients, else the registered bases, else the device vector
+        int rc = stage_input(ws, ws.h2d_points, coeffs, from ? (const void *)from->upoints.ptr : d_coeffs, bytes, {After::NOTHING}, &src);
+        if (rc) return rc;
         if ((d_coeffs || d_out_affine) && (rc = order_after(ws, caller))) return rc;  // the caller's stream owns those vectors
         void *dst = d_out_affine;
         if (!dst) {  // host output or a new registration: staged in h2d_points (the load has read any host input by then)
@@ -450,28 +426,15 @@ struct VTableOf {
         HIP_TRY(hipStreamSynchronize(ws.stream));
         return GMSM_OK;
     }
-    static constexpr decltype(GroupVTable::to_lagrange) lagrange_entry() {
-        if constexpr (IS_G1) return &to_lagrange;
-        else return nullptr;
-    }
     // ---- mpcsetup updates (gmsm_scale.h)
     static int batch_scale(Context &ctx, const uint64_t *points, const void *d_points, size_t n, const uint64_t *scalars, const void *d_scalars,
                            size_t n_scalars, const uint64_t *r, hipStream_t caller, uint64_t *out_affine, void *d_out_affine) {
         GMSM_LEASE_OR_FAIL(lease, ctx);
         Workspace &ws = *lease.w;
         const size_t bytes = n * G::AFF_BYTES;
-        int rc;
-        const void *src = d_points, *dsc = d_scalars;
-        if (points) {
-            if ((rc = ws.h2d_points.ensure(bytes))) return rc;
-            HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, points, bytes, hipMemcpyHostToDevice, ws.stream));
-            src = ws.h2d_points.ptr;
-        }
-        if (scalars) {
-            if ((rc = ws.h2d_scalars.ensure(n_scalars * sizeof(Fr)))) return rc;
-            HIP_TRY(hipMemcpyAsync(ws.h2d_scalars.ptr, scalars, n_scalars * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
-            dsc = ws.h2d_scalars.ptr;
-        }
+        const void *src, *dsc;
+        int rc = stage_input(ws, ws.h2d_points, points, d_points, bytes, {After::NOTHING}, &src);
+        if (rc || (rc = stage_input(ws, ws.h2d_scalars, scalars, d_scalars, n_scalars * sizeof(Fr), {After::NOTHING}, &dsc))) return rc;
         if ((d_points || d_scalars || d_out_affine) && (rc = order_after(ws, caller))) return rc;  // the caller's stream owns those vectors
         void *dst = d_out_affine;
         if (!dst) {  // host output: staged in h2d_points (the kernels have read any host input by the time it is written)
@@ -489,15 +452,9 @@ struct VTableOf {
                                    const uint64_t *r, hipStream_t caller, uint64_t *out_truncated_jac, uint64_t *out_shifted_jac) {
         GMSM_LEASE_OR_FAIL(lease, ctx);
         Workspace &ws = *lease.w;
-        int rc;
-        const void *src = d_points;
-        if (points) {
-            if ((rc = ws.h2d_points.ensure(n * G::AFF_BYTES))) return rc;
-            HIP_TRY(hipMemcpyAsync(ws.h2d_points.ptr, points, n * G::AFF_BYTES, hipMemcpyHostToDevice, ws.stream));
-            src = ws.h2d_points.ptr;
-        } else if ((rc = order_after(ws, caller))) {
-            return rc;
-        }
+        const void *src;
+        int rc = stage_input(ws, ws.h2d_points, points, d_points, n * G::AFF_BYTES, {After::STREAM, caller}, &src);
+        if (rc) return rc;
         Fr rr;
         memcpy(&rr, r, sizeof rr);
         typename G::J t, s;
@@ -508,13 +465,31 @@ struct VTableOf {
         return GMSM_OK;
     }
     static const GroupVTable *get() {
-        static const GroupVTable vt = {G::FR_BITS,      G::AFF_BYTES,   G::SCALAR_BYTES, sizeof(typename G::J),
-                                       sizeof(typename G::Ext), &multiexp_host, &multiexp_device, &window_sums,
-                                       &fold,           &jac_to_affine, &debug_decompose, &debug_field_op,
-                                       &debug_group_op, &generate_points, &register_bases, &submit, &collect, &window_sums_enqueue, &fold_sets, &fold_powers, &multiexp_bases_host, &batch_scalar_mul, &batch_jac_to_affine, &decode_raw, &validate_points, &decode_compressed, &encode_compressed, &fft_domain_new, &fft_run, &fft_bit_reverse, &precompute_tables, &tables_serve, &shard_piece, &host_piece_ranges, &debug_glv_split, &plan_info, &reduce_shape,
-                                       &poly_eval, &poly_div, &kzg_open, lagrange_entry(),
-                                       &fflonk_next_divisor, &open_check, &fflonk_fold, open_w_entry(), open_wprime_entry(), &batch_scale, &linear_combinations,
-                                       (unsigned)G::FrP::MAX_ORDER};
+        // Filled by name: several members have the same type (decode_raw / decode_compressed, fold / jac_to_affine), so a
+        // positional list with two of them swapped would compile.
+        static const GroupVTable vt = [] {
+            GroupVTable v{};
+            v.fr_bits = G::FR_BITS, v.fr_max_order = (unsigned)G::FrP::MAX_ORDER;
+            v.aff_bytes = G::AFF_BYTES, v.scalar_bytes = G::SCALAR_BYTES, v.jac_bytes = sizeof(typename G::J), v.xyzz_bytes = sizeof(typename G::Ext);
+#define GMSM_VT(f) v.f = &f
+            // In the order of the struct's members: the kernels of a group's code object are instantiated in the order their
+            // callers are first named here, so this order decides the object's layout.
+            GMSM_VT(multiexp_host), GMSM_VT(multiexp_device), GMSM_VT(window_sums), GMSM_VT(fold), GMSM_VT(jac_to_affine);
+            GMSM_VT(debug_decompose), GMSM_VT(debug_field_op), GMSM_VT(debug_group_op), GMSM_VT(generate_points);
+            GMSM_VT(register_bases), GMSM_VT(submit), GMSM_VT(collect), GMSM_VT(window_sums_enqueue), GMSM_VT(fold_sets), GMSM_VT(fold_powers);
+            GMSM_VT(multiexp_bases_host), GMSM_VT(batch_scalar_mul), GMSM_VT(batch_jac_to_affine);
+            GMSM_VT(decode_raw), GMSM_VT(validate_points), GMSM_VT(decode_compressed), GMSM_VT(encode_compressed);
+            GMSM_VT(fft_domain_new), GMSM_VT(fft_run), GMSM_VT(fft_bit_reverse);
+            GMSM_VT(precompute_tables), GMSM_VT(tables_serve), GMSM_VT(shard_piece), GMSM_VT(host_piece_ranges);
+            GMSM_VT(debug_glv_split), GMSM_VT(plan_info), GMSM_VT(reduce_shape);
+            GMSM_VT(poly_eval), GMSM_VT(poly_div), GMSM_VT(kzg_open);
+            if constexpr (IS_G1) GMSM_VT(to_lagrange);  // the three G1-only members stay null for the G2 groups
+            GMSM_VT(fflonk_next_divisor), GMSM_VT(open_check), GMSM_VT(fflonk_fold);
+            if constexpr (IS_G1) GMSM_VT(open_w), GMSM_VT(open_wprime);
+            GMSM_VT(batch_scale), GMSM_VT(linear_combinations);
+#undef GMSM_VT
+            return v;
+        }();
         return &vt;
     }
 };

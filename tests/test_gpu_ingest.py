@@ -200,6 +200,41 @@ def test_register_raw_then_multiexp(gm, oracle_mod, pyref_mod, curve, which):
     assert rb is None and "point 5" in err
 
 
+@pytest.mark.parametrize("curve,which", [("bn254", "g1"), ("bls12_381", "g2")])
+def test_decode_raw_to_device_then_validate_there(gm, oracle_mod, pyref_mod, curve, which):
+    """The device-pointer forms: gmsm_points_from_raw into device memory, gmsm_points_validate and gmsm_bases_register over
+    what it left there; a MultiExp over those bases equals the oracle's over the points that were encoded."""
+    import ctypes
+
+    import torch
+    g, pg = group_fixture(gm, pyref_mod, curve, which)
+    lib = gm._lib.load()
+    n = 40
+    pts = g.generate_points(n, 0xD0C0DE, 0x77)
+    pts[9] = 0  # infinity
+    raw = np.frombuffer(b"".join(encode_raw(pg, pg.point_from_limbs(pts[i])) for i in range(n)), dtype=np.uint8)
+    d_pts = torch.zeros((n, g.aff_limbs), dtype=torch.int64, device="cuda")
+    bad = ctypes.c_int64(7)
+    rc = lib.gmsm_points_from_raw(g.gid, raw.ctypes.data_as(ctypes.c_void_p), n, 2, None, d_pts.data_ptr(), ctypes.byref(bad))
+    assert rc == 0 and bad.value == -1
+    assert (d_pts.cpu().numpy().view(np.uint64) == pts).all()
+    for kw in ({}, {"subgroup_check": False}, {"by_definition": True}):
+        assert g.ValidatePoints(d_points=d_pts.data_ptr(), n=n, **kw) == (True, None)
+    rb = g.register_bases(d_points=d_pts.data_ptr(), n=n)
+    try:
+        sc = random_scalars(rng_for(5, n), g.curve, n)
+        jac, err = rb.MultiExp(sc)
+        assert err is None and (g.jac_to_affine(jac) == oracle_mod.Oracle(curve, which).msm_affine(pts, sc)).all()
+    finally:
+        rb.release()
+    # a point off the curve, on the device: Y of point 3 replaced by X (x^2 = x^3 + b has at most three roots)
+    off = pts.copy()
+    off[3, g.aff_limbs // 2:] = off[3, :g.aff_limbs // 2]
+    d_off = torch.from_numpy(off.view(np.int64)).cuda()
+    ok, err = g.ValidatePoints(d_points=d_off.data_ptr(), n=n, subgroup_check=False)
+    assert not ok and "point 3" in err and "not on the curve" in err
+
+
 def test_register_dump(gm, oracle_mod, tmp_path):
     """A file shaped like kzg.SRS.WriteDump's output (kzg/marshal.go:65-95): some verifying-key bytes, the marker, then
     unsafe.WriteSlice(pk.G1) = uint64 length + raw []G1Affine memory."""
