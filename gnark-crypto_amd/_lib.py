@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "gmsm_bases_register_dump", "gmsm_fft_domain_new", "gmsm_fft_domain_release", "gmsm_fft_domain_info", "gmsm_fft",
     "gmsm_fft_bit_reverse", "gmsm_poly_eval", "gmsm_poly_div_x_minus_a", "gmsm_kzg_open", "gmsm_kzg_open_folded",
     "gmsm_to_lagrange_g1", "gmsm_bases_to_lagrange", "gmsm_batch_scale", "gmsm_update_monomials", "gmsm_linear_combinations", "gmsm_shplonk_open_w", "gmsm_shplonk_open_wprime",
+    "gmsm_fr_batch_invert", "gmsm_iop_ratio_copy_constraint", "gmsm_iop_ratio_shuffled",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
     "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
@@ -201,6 +202,13 @@ def load():
     L.gmsm_fflonk_open_w.argtypes = [ctypes.c_uint64, u64p, vp, szp, szp, sz, u64p, szp, u64p, vp, u64p, u64p, u64p, vp, u64p]
     L.gmsm_fflonk_open_wprime.restype = ctypes.c_int
     L.gmsm_fflonk_open_wprime.argtypes = [ctypes.c_uint64, u64p, vp, szp, szp, sz, u64p, szp, u64p, u64p, u64p, vp, u64p, vp, u64p]
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    L.gmsm_fr_batch_invert.restype = ctypes.c_int
+    L.gmsm_fr_batch_invert.argtypes = [ctypes.c_int, u64p, vp, sz, vp, u64p, vp]
+    L.gmsm_iop_ratio_copy_constraint.restype = ctypes.c_int
+    L.gmsm_iop_ratio_copy_constraint.argtypes = [ctypes.c_uint64, u64p, vp, sz, u32p, vp, vp, u64p, u64p, ctypes.c_int, ctypes.c_int, vp, u64p, vp]
+    L.gmsm_iop_ratio_shuffled.restype = ctypes.c_int
+    L.gmsm_iop_ratio_shuffled.argtypes = [ctypes.c_uint64, u64p, vp, u64p, vp, sz, u32p, u32p, u64p, ctypes.c_int, ctypes.c_int, vp, u64p, vp]
     L.gmsm_get_stage_launches.restype = ctypes.c_int
     L.gmsm_get_stage_launches.argtypes = [vp, ctypes.c_int]
     ip = ctypes.POINTER(ctypes.c_int)

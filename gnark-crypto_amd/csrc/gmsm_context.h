@@ -570,6 +570,12 @@ static inline const char *point_status_text(uint32_t s) {
     }
 }
 
+// the refusal of a permutation value outside [0, m n) (gmsm_iop_ratio_copy_constraint; the reference panics there)
+static inline std::string ratio_perm_error(size_t index, long long value, size_t mn) {
+    return "gmsm_iop_ratio_copy_constraint: permutation[" + std::to_string(index) + "] = " + std::to_string(value) +
+           " is outside [0, " + std::to_string(mn) + ")";
+}
+
 // ------------------------------------------------------------------ window geometry
 static inline unsigned num_windows(unsigned fr_bits, unsigned c) { return (fr_bits + c - 1) / c; }  // multiexp.go:681
 static inline unsigned last_c(unsigned fr_bits, unsigned c) {                                         // multiexp.go:690
@@ -764,6 +770,16 @@ struct GroupVTable {
     // linearCombinationsG1/G2: the two sums over powers of r with zeros at the segment ends (checked by the caller), Jacobian
     int (*linear_combinations)(Context &ctx, const uint64_t *points, const void *d_points, size_t n, const size_t *ends, size_t n_ends,
                                const uint64_t *r, hipStream_t stream, uint64_t *out_truncated_jac, uint64_t *out_shifted_jac);
+    // fr.BatchInvert and the iop ratio polynomials over the group's scalar field (gmsm_ratio.h); nullptr for the G2 groups (the
+    // engine goes through the pair's G1 table). Vectors on the host or on the device as for poly_div; the m polynomials of
+    // n = the domain's cardinality elements are concatenated, in Lagrange basis, layouts[j] = 8 (Regular) / 16 (BitReverse).
+    int (*fr_batch_invert)(Context &ctx, const uint64_t *a, const void *d_a, size_t n, hipStream_t stream, uint64_t *out, void *d_out);
+    int (*ratio_copy)(Context &ctx, FftDomain *d, const uint64_t *entries, const void *d_entries, size_t m, const uint32_t *layouts,
+                      const int64_t *perm, const void *d_perm, const uint64_t *beta, const uint64_t *gamma, int basis, int layout,
+                      hipStream_t stream, uint64_t *out, void *d_out);
+    int (*ratio_shuffled)(Context &ctx, FftDomain *d, const uint64_t *num, const void *d_num, const uint64_t *den, const void *d_den,
+                          size_t m, const uint32_t *num_layouts, const uint32_t *den_layouts, const uint64_t *beta, int basis, int layout,
+                          hipStream_t stream, uint64_t *out, void *d_out);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

@@ -1618,6 +1618,110 @@ GMSM_EXPORT int gmsm_linear_combinations(int group, const uint64_t *points, cons
     return vt->linear_combinations(*ctx, points, d_points, n, ends, n_ends, r, (hipStream_t)hip_stream, out_truncated_jac, out_shifted_jac);
 }
 
+// ------------------------------------------------------------------ fr.BatchInvert, iop ratio polynomials (gmsm_ratio.h)
+// the scalar field's entries live in the table of the pair's G1 group (even id)
+static const GroupVTable *fr_vtable(int group) { return vtable(group) ? vtable(group & ~1) : nullptr; }
+
+GMSM_EXPORT int gmsm_fr_batch_invert(int group, const uint64_t *a, const void *d_a, size_t n, void *hip_stream, uint64_t *out, void *d_out) {
+    const GroupVTable *vt = fr_vtable(group);
+    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    const char *E = "gmsm_fr_batch_invert";
+    if (n == 0) return GMSM_OK;
+    if ((a == nullptr) == (d_a == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of a (host) / d_a (device)");
+    if ((out == nullptr) == (d_out == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out (host) / d_out (device)");
+    Context *ctx;
+    int rc = enter_owner(d_a ? d_a : d_out, &ctx);
+    if (rc) return rc;
+    if ((rc = check_device_vector(E, "d_a", d_a, ctx->device)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
+    return vt->fr_batch_invert(*ctx, a, d_a, n, (hipStream_t)hip_stream, out, d_out);
+}
+
+// The host checks of the two ratio entries, in this order: what needs nothing but the arguments - the count, the expected form,
+// the output pair (ratio_form), then the entry's own pointers, pairs and layout values - then the domain handle (ratio_domain),
+// then what needs the domain's cardinality: the overlap of the output with an input, the range of a host permutation.
+static int ratio_form(const char *E, size_t m, int basis, int layout, uint64_t *out, void *d_out) {
+    if (m == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": no polynomial (m == 0)");
+    if (basis != 1 && basis != 2 && basis != 4)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": unknown basis " + std::to_string(basis) + " (1 Canonical, 2 Lagrange, 4 LagrangeCoset)");
+    if (layout != 8 && layout != 16)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": unknown layout " + std::to_string(layout) + " (8 Regular, 16 BitReverse)");
+    if ((out == nullptr) == (d_out == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of out (host) / d_out (device)");
+    return GMSM_OK;
+}
+static int ratio_layouts(const char *E, const char *name, const uint32_t *layouts, size_t m) {
+    if (!layouts) return fail(GMSM_ERR_ARG, std::string(E) + ": " + name + " is null");
+    for (size_t j = 0; j < m; ++j)
+        if (layouts[j] != 8 && layouts[j] != 16)
+            return fail(GMSM_ERR_ARG, std::string(E) + ": " + name + "[" + std::to_string(j) + "] = " + std::to_string(layouts[j]) +
+                                          " is no layout (8 Regular, 16 BitReverse)");
+    return GMSM_OK;
+}
+static int ratio_pair(const char *E, const char *host, const char *dev, const void *h, const void *d) {
+    if ((h == nullptr) == (d == nullptr))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of " + host + " (host) / " + dev + " (device)");
+    return GMSM_OK;
+}
+static int ratio_domain(const char *E, uint64_t domain, size_t m, FftRef *d_out_ref, const GroupVTable **vt_out) {
+    FftRef d = g_fft.get(domain);
+    if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
+    if (m > (((size_t)1 << 62) >> d->log2n)) return fail(GMSM_ERR_ARG, std::string(E) + ": m * n does not fit");
+    *d_out_ref = d, *vt_out = fr_vtable(d->group);
+    return GMSM_OK;
+}
+// the output (host or device, out_bytes) shares a byte with an input vector of in_bytes on the same side
+static bool ratio_overlap(const void *out, const void *d_out, size_t out_bytes, const void *in, const void *d_in, size_t in_bytes) {
+    const uintptr_t o = (uintptr_t)(out ? out : d_out), i = (uintptr_t)(out ? in : d_in);
+    return i != 0 && o < i + in_bytes && i < o + out_bytes;
+}
+static int ratio_aliases(const char *E) { return fail(GMSM_ERR_ARG, std::string(E) + ": the output overlaps an input (inputs are never modified)"); }
+
+GMSM_EXPORT int gmsm_iop_ratio_copy_constraint(uint64_t domain, const uint64_t *entries, const void *d_entries, size_t m, const uint32_t *layouts,
+                                               const int64_t *perm, const void *d_perm, const uint64_t *beta, const uint64_t *gamma, int basis,
+                                               int layout, void *hip_stream, uint64_t *out, void *d_out) {
+    const char *E = "gmsm_iop_ratio_copy_constraint";
+    int rc = ratio_form(E, m, basis, layout, out, d_out);
+    if (rc || (rc = ratio_layouts(E, "layouts", layouts, m))) return rc;
+    if (!beta || !gamma) return fail(GMSM_ERR_ARG, std::string(E) + ": beta and gamma must not be null");
+    if ((rc = ratio_pair(E, "entries", "d_entries", entries, d_entries)) || (rc = ratio_pair(E, "perm", "d_perm", perm, d_perm))) return rc;
+    FftRef d;
+    const GroupVTable *vt;
+    if ((rc = ratio_domain(E, domain, m, &d, &vt))) return rc;
+    const size_t mn = m << d->log2n, zbytes = vt->scalar_bytes << d->log2n;
+    if (ratio_overlap(out, d_out, zbytes, entries, d_entries, m * zbytes) || ratio_overlap(out, d_out, zbytes, perm, d_perm, mn * 8))
+        return ratio_aliases(E);
+    if (perm)  // a permutation on the device is checked by the factor kernel
+        for (size_t i = 0; i < mn; ++i)
+            if (perm[i] < 0 || (uint64_t)perm[i] >= mn) return fail(GMSM_ERR_ARG, ratio_perm_error(i, perm[i], mn));
+    Context *ctx;
+    if ((rc = enter_on(d->device, &ctx))) return rc;  // the domain decides the device
+    if ((rc = check_device_vector(E, "d_entries", d_entries, ctx->device)) || (rc = check_device_vector(E, "d_perm", d_perm, ctx->device)) ||
+        (rc = check_device_vector(E, "d_out", d_out, ctx->device)))
+        return rc;
+    return vt->ratio_copy(*ctx, d.get(), entries, d_entries, m, layouts, perm, d_perm, beta, gamma, basis, layout, (hipStream_t)hip_stream, out, d_out);
+}
+
+GMSM_EXPORT int gmsm_iop_ratio_shuffled(uint64_t domain, const uint64_t *num, const void *d_num, const uint64_t *den, const void *d_den, size_t m,
+                                        const uint32_t *num_layouts, const uint32_t *den_layouts, const uint64_t *beta, int basis, int layout,
+                                        void *hip_stream, uint64_t *out, void *d_out) {
+    const char *E = "gmsm_iop_ratio_shuffled";
+    int rc = ratio_form(E, m, basis, layout, out, d_out);
+    if (rc || (rc = ratio_layouts(E, "num_layouts", num_layouts, m)) || (rc = ratio_layouts(E, "den_layouts", den_layouts, m))) return rc;
+    if (!beta) return fail(GMSM_ERR_ARG, std::string(E) + ": beta must not be null");
+    if ((rc = ratio_pair(E, "num", "d_num", num, d_num)) || (rc = ratio_pair(E, "den", "d_den", den, d_den))) return rc;
+    FftRef d;
+    const GroupVTable *vt;
+    if ((rc = ratio_domain(E, domain, m, &d, &vt))) return rc;
+    const size_t zbytes = vt->scalar_bytes << d->log2n;
+    if (ratio_overlap(out, d_out, zbytes, num, d_num, m * zbytes) || ratio_overlap(out, d_out, zbytes, den, d_den, m * zbytes)) return ratio_aliases(E);
+    Context *ctx;
+    if ((rc = enter_on(d->device, &ctx))) return rc;  // the domain decides the device
+    if ((rc = check_device_vector(E, "d_num", d_num, ctx->device)) || (rc = check_device_vector(E, "d_den", d_den, ctx->device)) ||
+        (rc = check_device_vector(E, "d_out", d_out, ctx->device)))
+        return rc;
+    return vt->ratio_shuffled(*ctx, d.get(), num, d_num, den, d_den, m, num_layouts, den_layouts, beta, basis, layout, (hipStream_t)hip_stream, out,
+                              d_out);
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {

@@ -24,6 +24,7 @@
 #include "gmsm_fflonk.h"
 #include "gmsm_group_fft.h"
 #include "gmsm_scale.h"
+#include "gmsm_ratio.h"
 
 namespace gmsm {
 

@@ -464,6 +464,151 @@ struct VTableOf {
         memcpy(out_shifted_jac, &s, sizeof s);
         return GMSM_OK;
     }
+    // ---- fr.BatchInvert and the iop ratio polynomials (gmsm_ratio.h); in the G1 tables only: the scalar field is the pair's
+    using RF = RatioField<typename G::FrP>;
+    static int fr_batch_invert(Context &ctx, const uint64_t *a, const void *d_a, size_t n, hipStream_t caller, uint64_t *out, void *d_out) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const Fr *in;
+        int rc = poly_input(ws, a, d_a, n, caller, &in);
+        if (rc) return rc;
+        if (d_out && a && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out
+        if ((rc = ws.poly.ensure((n + (out ? n : 0)) * sizeof(Fr)))) return rc;
+        Fr *run = (Fr *)ws.poly.ptr, *res = out ? run + n : (Fr *)d_out;
+        if ((rc = RF::invert(ws.stream, in, n, run, nullptr, res, PF::lane_option()))) return rc;
+        if (out) HIP_TRY(hipMemcpyAsync(out, res, n * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    // The scratch of a ratio call in ws.poly: the two factor vectors (N and D after the scan), the inversion's running
+    // products, the scan's lane and tile values, then `tail` more elements for the call's small tables.
+    struct RatioBuffers {
+        Fr *fnum, *fden, *run, *scan, *tail;
+        unsigned lanes;
+    };
+    static int ratio_buffers(Workspace &ws, size_t n, size_t tail, RatioBuffers *b) {
+        b->lanes = PF::lane_option();
+        const size_t scan = RF::scan_scratch(n, b->lanes);
+        if (int rc = ws.poly.ensure((3 * n + scan + tail) * sizeof(Fr))) return rc;
+        b->fnum = (Fr *)ws.poly.ptr, b->fden = b->fnum + n, b->run = b->fden + n, b->scan = b->run + n, b->tail = b->scan + scan;
+        return GMSM_OK;
+    }
+    // holds a call's pageable staging vectors until its stream has drained, whichever way the call leaves
+    struct DrainOnExit {
+        hipStream_t s;
+        ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+    };
+    // The workspace's stage events are about to be recorded anew: events that an enqueue-only MultiExp left for the next call
+    // to read are read now or dropped, as the MultiExp path does, so a ratio call that leaves early never hands mixed pairs on.
+    static void ratio_settle_events(Workspace &ws) {
+        if (!ws.uncollected) return;
+        if (ws.timed && hipEventQuery(ws.events[ws.timed_level == 2 ? T_FIXUP : T_END]) == hipSuccess) StageTimer::collect(ws);
+        ws.uncollected = false;
+    }
+    // From the factor vectors to the result: prefix products, Z = N inv0(D), the expected form, the copy-out. With profiling
+    // at level 1 the call's stage times go to the slots 0 (factors), 2 (product scan), 5 (inversion and multiply) and 6 (the
+    // expected form's transforms); `timer` has marked T_DECOMPOSE before the factor kernel.
+    // bad != null (a permutation on the device, checked by the factor kernel): the pipeline runs on without waiting for the
+    // verdict - it writes scratch only - and the one synchronise at the end brings *first_bad back with everything else; a
+    // device output is written by k_ratio_publish, which writes nothing when the check failed, a host output after the verdict.
+    static int ratio_finish(Workspace &ws, StageTimer &timer, FftDomain *d, const RatioBuffers &b, size_t n, int basis, int layout,
+                            uint64_t *out, void *d_out, const unsigned long long *bad, unsigned long long *first_bad) {
+        hipStream_t s = ws.stream;
+        timer.mark(T_HIST, s), timer.mark(T_SCAN, s);
+        int rc = RF::scan2(s, b.fnum, b.fden, n, b.scan, b.lanes);
+        if (rc) return rc;
+        timer.mark(T_SCATTER, s), timer.mark(T_ACCUMULATE, s), timer.mark(T_FIXUP, s);
+        Fr *z = d_out && !bad ? (Fr *)d_out : b.fnum;
+        if ((rc = RF::invert(s, b.fden, n, b.run, b.fnum, z, b.lanes))) return rc;
+        timer.mark(T_REDUCE, s);
+        if ((rc = RF::expected_form(s, d, z, basis, (uint32_t)layout))) return rc;
+        if (bad && d_out) {
+            hipLaunchKernelGGL((k_ratio_publish<typename G::FrP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const Fr *)z, (Fr *)d_out, n, bad);
+            HIP_TRY(hipGetLastError());
+        }
+        timer.mark(T_END, s);
+        if (bad) HIP_TRY(hipMemcpyAsync(first_bad, bad, sizeof *first_bad, hipMemcpyDeviceToHost, s));
+        else if (out) HIP_TRY(hipMemcpyAsync(out, z, n * sizeof(Fr), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (bad && *first_bad != ~0ull) return GMSM_OK;  // the caller refuses; nothing was written to the output
+        if (bad && out) {
+            HIP_TRY(hipMemcpyAsync(out, z, n * sizeof(Fr), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        if (timer.level == 1) StageTimer::collect(ws);
+        return GMSM_OK;
+    }
+    static int ratio_copy(Context &ctx, FftDomain *d, const uint64_t *entries, const void *d_entries, size_t m, const uint32_t *layouts,
+                          const int64_t *perm, const void *d_perm, const uint64_t *beta, const uint64_t *gamma, int basis, int layout,
+                          hipStream_t caller, uint64_t *out, void *d_out) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const size_t n = (size_t)1 << d->log2n;
+        const Fr *in;
+        const void *pm;
+        int rc = poly_input(ws, entries, d_entries, m * n, caller, &in);
+        if (rc || (rc = stage_input(ws, ws.h2d_points, perm, d_perm, m * n * 8, {After::STREAM, caller}, &pm))) return rc;
+        if (d_out && entries && perm && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out
+        const size_t lay_slots = word_slots((m + 1) / 2);
+        RatioBuffers b;
+        if ((rc = ratio_buffers(ws, n, m + lay_slots + 1, &b))) return rc;
+        Fr *bg = b.tail;
+        uint32_t *lay = (uint32_t *)(bg + m);
+        unsigned long long *bad = (unsigned long long *)(bg + m + lay_slots);
+        Fr bt, gm;
+        memcpy(&bt, beta, sizeof bt);
+        memcpy(&gm, gamma, sizeof gm);
+        std::vector<Fr> table(m);
+        RF::coset_table(d, bt, m, table.data());
+        const unsigned long long none = ~0ull;
+        unsigned long long first_bad = none;
+        DrainOnExit drain{ws.stream};
+        HIP_TRY(hipMemcpyAsync(bg, table.data(), m * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+        HIP_TRY(hipMemcpyAsync(lay, layouts, m * sizeof(uint32_t), hipMemcpyHostToDevice, ws.stream));
+        HIP_TRY(hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, ws.stream));
+        ratio_settle_events(ws);
+        StageTimer timer(ws, true);
+        timer.mark(T_DECOMPOSE, ws.stream);
+        hipLaunchKernelGGL((k_ratio_factors_copy<typename G::FrP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ws.stream, in,
+                           (const uint32_t *)lay, m, n, d->log2n, (const long long *)pm, (const Fr *)d->twiddles_lz.ptr, (const Fr *)bg, gm, b.fnum,
+                           b.fden, bad);
+        HIP_TRY(hipGetLastError());
+        // a host permutation was checked before it was staged; one on the device: the factor kernel's verdict, read at the end
+        if ((rc = ratio_finish(ws, timer, d, b, n, basis, layout, out, d_out, d_perm ? bad : nullptr, &first_bad))) return rc;
+        if (first_bad != none) {
+            long long v = 0;
+            HIP_TRY(hipMemcpy(&v, (const long long *)d_perm + first_bad, sizeof v, hipMemcpyDeviceToHost));
+            return fail(GMSM_ERR_ARG, ratio_perm_error((size_t)first_bad, v, m * n));
+        }
+        return GMSM_OK;
+    }
+    static int ratio_shuffled(Context &ctx, FftDomain *d, const uint64_t *num, const void *d_num, const uint64_t *den, const void *d_den,
+                              size_t m, const uint32_t *num_layouts, const uint32_t *den_layouts, const uint64_t *beta, int basis, int layout,
+                              hipStream_t caller, uint64_t *out, void *d_out) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const size_t n = (size_t)1 << d->log2n;
+        const Fr *pn;
+        const void *pd;
+        int rc = poly_input(ws, num, d_num, m * n, caller, &pn);
+        if (rc || (rc = stage_input(ws, ws.h2d_points, den, d_den, m * n * sizeof(Fr), {After::STREAM, caller}, &pd))) return rc;
+        if (d_out && num && den && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out
+        RatioBuffers b;
+        if ((rc = ratio_buffers(ws, n, word_slots(m), &b))) return rc;
+        uint32_t *lay = (uint32_t *)b.tail;
+        Fr bt;
+        memcpy(&bt, beta, sizeof bt);
+        DrainOnExit drain{ws.stream};
+        HIP_TRY(hipMemcpyAsync(lay, num_layouts, m * sizeof(uint32_t), hipMemcpyHostToDevice, ws.stream));
+        HIP_TRY(hipMemcpyAsync(lay + m, den_layouts, m * sizeof(uint32_t), hipMemcpyHostToDevice, ws.stream));
+        ratio_settle_events(ws);
+        StageTimer timer(ws, true);
+        timer.mark(T_DECOMPOSE, ws.stream);
+        hipLaunchKernelGGL((k_ratio_factors_shuffled<typename G::FrP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ws.stream, pn,
+                           (const Fr *)pd, (const uint32_t *)lay, m, n, d->log2n, bt, b.fnum, b.fden);
+        HIP_TRY(hipGetLastError());
+        return ratio_finish(ws, timer, d, b, n, basis, layout, out, d_out, nullptr, nullptr);
+    }
     static const GroupVTable *get() {
         // Filled by name: several members have the same type (decode_raw / decode_compressed, fold / jac_to_affine), so a
         // positional list with two of them swapped would compile.
@@ -487,6 +632,7 @@ struct VTableOf {
             GMSM_VT(fflonk_next_divisor), GMSM_VT(open_check), GMSM_VT(fflonk_fold);
             if constexpr (IS_G1) GMSM_VT(open_w), GMSM_VT(open_wprime);
             GMSM_VT(batch_scale), GMSM_VT(linear_combinations);
+            if constexpr (IS_G1) GMSM_VT(fr_batch_invert), GMSM_VT(ratio_copy), GMSM_VT(ratio_shuffled);
 #undef GMSM_VT
             return v;
         }();

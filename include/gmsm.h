@@ -420,6 +420,46 @@ int gmsm_linear_combinations(int group, const uint64_t *points, const void *d_po
                              const size_t *ends, size_t n_ends, const uint64_t *r, void *hip_stream,
                              uint64_t *out_truncated_jac, uint64_t *out_shifted_jac);
 
+/* ---- fr.BatchInvert (ecc/<curve>/fr/element.go:658-687) and PLONK's accumulating-ratio polynomials
+ *      (ecc/<curve>/fr/iop/ratios.go: BuildRatioCopyConstraint :136-246, BuildRatioShuffledVectors :45-127) on the device
+ *      (gmsm_ratio.h): a factor kernel, two prefix-product scans run side by side, Montgomery's trick per tile, the expected
+ *      form through the FFT and bit-reverse kernels. Results are bit-identical to the reference's: every output is a uniquely
+ *      determined canonical fr.Element.
+ *   Conventions, those of the KZG entries: Montgomery fr.Element limbs; exactly one of each host / device pointer pair;
+ *      device pointers 16-byte aligned and produced on hip_stream; inputs are never modified; the call returns when its
+ *      result is complete; scratch comes from the call's workspace. A G2 group id names its curve's scalar field as well.
+ *   gmsm_fr_batch_invert: out[i] = 1 / a[i], and 0 where a[i] = 0 (the reference's zero rule). The output may alias the
+ *      input. n == 0 is GMSM_OK and touches nothing.
+ *   gmsm_iop_ratio_copy_constraint: `domain` is a gmsm_fft_domain_new handle and n its cardinality. `entries` holds m
+ *      polynomials of n elements, concatenated, in LAGRANGE basis - the reference's ToLagrange on the inputs
+ *      (polynomial.go:287-318) stays with the caller, through gmsm_fft - with layouts[j] (host) = 8 (Regular) or 16
+ *      (BitReverse), the reference's values; `perm` holds m n int64 values in [0, m n). The result Z has Z_0 = 1 and
+ *        Z_(i+1) = Z_i prod_j (P_j(w^i) + beta S[i + j n] + gamma) / (P_j(w^i) + beta S[perm[i + j n]] + gamma),
+ *      S[p] = g^(p div n) w^(p mod n) the support of getSupportIdentityPermutation (g = FrMultiplicativeGen; read from the
+ *      domain's twiddles, never built); where a denominator product is zero, Z is 0 from the next index on - what the
+ *      reference's BatchInvert gives. Z is then put in the expected form (basis 1 Canonical, 2 Lagrange, 4 LagrangeCoset;
+ *      layout 8 Regular, 16 BitReverse) as putInExpectedFormFromLagrangeRegular does (ratios.go:248-273) and written, n
+ *      elements, to out / d_out. n = 1 returns [1] in the expected form.
+ *   gmsm_iop_ratio_shuffled: Z_(i+1) = Z_i prod_j (beta - P_j(w^i)) / (beta - Q_j(w^i)) over m numerators and m
+ *      denominators, each with its own layout; everything else as above.
+ *   Errors are GMSM_ERR_ARG with a text, before any device work where the host can decide: m == 0; a null required
+ *      pointer, or both or none of a pair; an unknown domain handle ("unknown fft domain handle"); an unknown basis or
+ *      layout value; an output whose n elements overlap an input of a ratio entry, wholly or in part (host with host,
+ *      device with device); a perm value outside [0, m n) - the reference panics
+ *      there: "...: permutation[i] = v is outside [0, m n)" names the first such index (a permutation on the device is
+ *      checked by the factor kernel; nothing is written to the output then).
+ *   With gmsm_set_profiling(1) a ratio call adds its stage times to the slots 0 (factor kernel), 2 (the prefix products),
+ *      5 (inversion and final multiply) and 6 (the transforms of the expected form) of gmsm_get_stage_times. ---- */
+int gmsm_fr_batch_invert(int group, const uint64_t *a, const void *d_a, size_t n, void *hip_stream,
+                         uint64_t *out, void *d_out);
+int gmsm_iop_ratio_copy_constraint(uint64_t domain, const uint64_t *entries, const void *d_entries, size_t m,
+                                   const uint32_t *layouts, const int64_t *perm, const void *d_perm,
+                                   const uint64_t *beta, const uint64_t *gamma, int basis, int layout,
+                                   void *hip_stream, uint64_t *out, void *d_out);
+int gmsm_iop_ratio_shuffled(uint64_t domain, const uint64_t *num, const void *d_num, const uint64_t *den,
+                            const void *d_den, size_t m, const uint32_t *num_layouts, const uint32_t *den_layouts,
+                            const uint64_t *beta, int basis, int layout, void *hip_stream, uint64_t *out, void *d_out);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals
@@ -530,7 +570,8 @@ enum gmsm_option {
                                  and the gmsm_shplonk_open entries: 0 (default) = lanes of 8, 16 or 32 coefficients by length; k in 1..6 =
                                  lanes of 2^(k-1) coefficients whatever the length (a tile is 256 lanes, so k = 1 reaches the
                                  carry pass's lanes of several tiles at 2^16 coefficients instead of 2^21). Cost only: every
-                                 output is the same field element. Read once per call. */
+                                 output is the same field element. Read once per call. The prefix products and the batch inversion
+                                 behind gmsm_fr_batch_invert and the gmsm_iop_ratio entries cut their vectors the same way. */
     GMSM_OPT_REDUCE_SHAPE = 12 /* for the tests of the bucket reduction's launch shapes: 0 (default) = the cost model. A packed value:
                                  bits 0-3 log2L (1..8 buckets per serial segment as a power of two, 0 = model), bits 4-5 the levels
                                  (2 = serial, combine, level 2; 3 = a second combine in between; 0 = model), bits 6-7 the combine kernel
