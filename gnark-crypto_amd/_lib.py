@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "gmsm_to_lagrange_g1", "gmsm_bases_to_lagrange", "gmsm_batch_scale", "gmsm_update_monomials", "gmsm_linear_combinations", "gmsm_shplonk_open_w", "gmsm_shplonk_open_wprime",
     "gmsm_fr_batch_invert", "gmsm_iop_ratio_copy_constraint", "gmsm_iop_ratio_shuffled",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
-    "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
+    "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_debug_fold_planes", "gmsm_debug_plane_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
     "gmsm_device_count", "gmsm_set_device", "gmsm_last_error",
     "gmsm_version",
@@ -92,6 +92,10 @@ def load():
     L.gmsm_debug_table_runs.argtypes = []
     L.gmsm_debug_small_runs.restype = ctypes.c_ulong
     L.gmsm_debug_small_runs.argtypes = []
+    L.gmsm_debug_plane_runs.restype = ctypes.c_ulong
+    L.gmsm_debug_plane_runs.argtypes = []
+    L.gmsm_debug_fold_planes.restype = ctypes.c_int
+    L.gmsm_debug_fold_planes.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, u64p, u64p]
     L.gmsm_debug_reduce_shape.restype = ctypes.c_int
     L.gmsm_debug_reduce_shape.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     L.gmsm_multiexp_bases.restype = ctypes.c_int
@@ -259,7 +263,7 @@ def last_error():
 
 # enum gmsm_option (include/gmsm.h)
 OPTIONS = {"window_bits": 0, "tables": 1, "max_run": 2, "host_ranges": 3, "fixed_base_bits": 4, "spin_wait_us": 5, "small_bits": 6, "small_max": 7, "split": 8, "glv": 9, "small_quad": 10,
-           "poly_lane_bits": 11, "reduce_shape": 12}
+           "poly_lane_bits": 11, "reduce_shape": 12, "reduce_tail": 13}
 
 
 def set_option(name, value):

@@ -71,11 +71,13 @@ struct Options {
     std::atomic<unsigned> small_quad{0};       // GMSM_OPT_SMALL_QUAD: bucket phase of the fused kernel on lane quads: 0 by size, 1 never (narrow types), 2 always
     std::atomic<unsigned> poly_lane_bits{0};   // GMSM_OPT_POLY_LANE_BITS (tests): 0 = lane width of the suffix scan by length, k in 1..6 = 2^(k-1) coefficients
     std::atomic<unsigned> reduce_shape{0};     // GMSM_OPT_REDUCE_SHAPE (tests): 0 = the reduction's cost model; packed log2L | levels << 4 | combine kernel << 6
+    std::atomic<unsigned> reduce_tail{0};      // GMSM_OPT_REDUCE_TAIL: who scales the reduction's sums: 0 by group and call, 1 the device (ladder), 2 the host fold (planes)
 };
 Options &options();
 
 extern std::atomic<unsigned long> g_small_runs;  // calls served by the fused small-n kernel (gmsm_debug_small_runs)
 extern std::atomic<unsigned long> g_table_runs;  // pipeline runs that went through window tables (gmsm_debug_table_runs)
+extern std::atomic<unsigned long> g_plane_runs;  // pipeline runs whose reduction ended in k_plane_sums (gmsm_debug_plane_runs)
 
 // Bases rewritten once into the lazy Montgomery domain and kept in HBM (gmsm_bases_register): the resident-SRS path.
 // Shared ownership (std::shared_ptr): the handle table holds one reference, every call and every outstanding ticket
@@ -179,6 +181,9 @@ struct Workspace {
     int timed_level = 0;                // ... at this profiling level (1: every stage, 2: the accumulation kernel only)
     void *pinned = nullptr;             // pinned host buffer for the window totals
     size_t pinned_cap = 0;
+    // what the last enqueue leaves in `pinned`: plane_np == 0 the window totals; else plane_np = 7 + nhigh planes per window
+    // (k_plane_sums; Group::fold_planes applies the weights, which start at 2^plane_log2L)
+    uint32_t plane_np = 0, plane_log2L = 0;
     DeviceBuffer h2d_points, h2d_scalars;  // staging of the host-pointer entries
     DeviceBuffer raw_bytes, flagword;      // point ingest: wire-format bytes, first-offender word
     DeviceBuffer poly;                     // KZG opening (gmsm_poly.h): folded polynomial, quotient, lane and tile carries
@@ -726,6 +731,7 @@ struct GroupVTable {
     int (*debug_glv_split)(const uint64_t *scalars, size_t n, uint32_t *out);  // test hook of gmsm_glv.h
     void (*plan_info)(size_t n, unsigned *c, unsigned *nwin, unsigned *entries_per_point, unsigned *fused);  // gmsm_default_plan
     void (*reduce_shape)(const Context &ctx, uint32_t nw, uint32_t nbuckets, uint32_t out[6]);  // gmsm_debug_reduce_shape
+    void (*fold_planes)(const uint64_t *planes, unsigned c, unsigned nwin, unsigned log2L, unsigned nhigh, uint64_t *out_jac);  // gmsm_debug_fold_planes
     // KZG opening over the group's scalar field (gmsm_poly.h): polynomials are host (`polys`) or device (`d_polys`) fr.Element
     // vectors, k of them concatenated (lens[i] elements each), never modified
     int (*poly_eval)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,

@@ -24,6 +24,7 @@ static thread_local int g_device = -1;
 static std::atomic<int> g_default_device{0};
 std::atomic<unsigned long> g_table_runs{0};
 std::atomic<unsigned long> g_small_runs{0};
+std::atomic<unsigned long> g_plane_runs{0};
 static std::atomic<uint32_t> g_ticket_gen{0};  // ticket generations: process-wide and monotonic, so a ticket of before a gmsm_shutdown never matches one issued after it
 
 // Process-wide switches; GMSM_C and GMSM_TABLES are read here ONCE (first use), never on a call path.
@@ -922,6 +923,7 @@ GMSM_EXPORT int gmsm_bases_precompute(uint64_t handle, unsigned c) {
 
 GMSM_EXPORT unsigned long gmsm_debug_table_runs(void) { return g_table_runs.load(); }
 GMSM_EXPORT unsigned long gmsm_debug_small_runs(void) { return g_small_runs.load(); }
+GMSM_EXPORT unsigned long gmsm_debug_plane_runs(void) { return g_plane_runs.load(); }
 
 // 0 = no tables; else the window width of the handle's tables
 GMSM_EXPORT unsigned gmsm_bases_table_bits(uint64_t handle) {
@@ -1779,6 +1781,17 @@ GMSM_EXPORT int gmsm_debug_reduce_shape(int group, uint32_t nw, uint32_t nbucket
     return GMSM_OK;
 }
 
+GMSM_EXPORT int gmsm_debug_fold_planes(int group, unsigned c, unsigned nwin, unsigned log2L, unsigned nblocks1, const uint64_t *planes,
+                                       uint64_t *out_jac) {
+    VT_OR_FAIL(group);
+    if (c < 2 || c > 24 || nwin == 0 || nwin > 512 || log2L > 8 || nblocks1 == 0 || nblocks1 > 128 || !planes || !out_jac)
+        return fail(GMSM_ERR_ARG, "gmsm_debug_fold_planes: 2 <= c <= 24, 1 <= nwin <= 512, log2L <= 8, 1 <= nblocks1 <= 128");
+    unsigned nhigh = 0;
+    while ((1u << nhigh) < nblocks1) ++nhigh;
+    vt->fold_planes(planes, c, nwin, log2L, nhigh, out_jac);
+    return GMSM_OK;
+}
+
 GMSM_EXPORT unsigned gmsm_num_windows(int group, unsigned c) {
     const GroupVTable *vt = vtable(group);
     return (vt && c) ? num_windows(vt->fr_bits, c) : 0;
@@ -1973,6 +1986,8 @@ static const OptionRow OPTION_ROWS[] = {
     {GMSM_OPT_REDUCE_SHAPE, &Options::reduce_shape,
      [](unsigned v) { return !(v > 255 || (v & 15u) > 8 || ((v >> 4) & 3u) == 1 || ((v >> 6) & 3u) == 3); },
      "GMSM_OPT_REDUCE_SHAPE: 0 (the cost model) or log2L (0, 1..8) | levels (0, 2, 3) << 4 | combine kernel (0, 1, 2) << 6"},
+    {GMSM_OPT_REDUCE_TAIL, &Options::reduce_tail, [](unsigned v) { return v <= 2; },
+     "GMSM_OPT_REDUCE_TAIL: 0 by group and call, 1 the device ladder, 2 the host planes"},
     {GMSM_OPT_SPIN_WAIT_US, &Options::spin_wait_us, [](unsigned v) { return v <= 1000000; }, "GMSM_OPT_SPIN_WAIT_US: at most 1000000"},
 };
 static const OptionRow *option_row(int key) {

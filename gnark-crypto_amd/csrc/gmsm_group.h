@@ -48,6 +48,7 @@ struct Group : GroupHost<F_, FrP_> {
     using Host::batch_to_affine;
     using Host::build_fixed_base_table;
     using Host::fold;
+    using Host::fold_planes;
     using Host::fold_powers;
     using Host::fold_sets;
     using Host::generate_points;
@@ -159,10 +160,34 @@ struct Group : GroupHost<F_, FrP_> {
                            const ResidentBases *resident = nullptr, size_t resident_offset = 0) {
         int rc = order_after(ws, caller_stream);
         if (rc) return rc;
-        if ((rc = enqueue_window_sums(ctx, ws, d_points, d_scalars, n, plan, ws.stream, resident, nullptr, resident_offset)))
+        if ((rc = enqueue_window_sums(ctx, ws, d_points, d_scalars, n, plan, ws.stream, resident, nullptr, resident_offset,
+                                      false, false, TAIL_IF_FORCED)))
             return rc;
         return collect_window_sums(ws, ws.stream, plan.nwin_local, host_xyzz);
     }
+    // The same for a caller that wants the folded MultiExp: the reduction may leave its scaling to the host fold.
+    static int window_sums_folded(Context &ctx, Workspace &ws, const void *d_points, const void *d_scalars, size_t n,
+                                  const WindowPlan &plan, hipStream_t caller_stream, J *out, const ResidentBases *resident) {
+        int rc = order_after(ws, caller_stream);
+        if (rc) return rc;
+        if ((rc = enqueue_window_sums(ctx, ws, d_points, d_scalars, n, plan, ws.stream, resident, nullptr, 0, false, false, TAIL_AUTO)))
+            return rc;
+        return collect_folded(ws, ws.stream, plan.c, plan.nwin_total, out);
+    }
+
+    // GMSM_OPT_REDUCE_TAIL: what a caller of enqueue_window_sums can take from ws.pinned - window totals only, plane sums
+    // when the option forces them (it converts them to totals itself: collect_window_sums), plane sums whenever they pay
+    // (it folds on the host: collect_folded).
+    enum { TAIL_LADDER = 0, TAIL_IF_FORCED = 1, TAIL_AUTO = 2 };
+#ifndef GMSM_PLANES_AUTO_WORDS
+#define GMSM_PLANES_AUTO_WORDS 9
+#endif
+    // groups whose MultiExp entries take the host planes by default: BN254 G1 (the 9-limb field), measured in
+    // profiles/reduce_planes_ab.md; the plane kernels exist for the groups that have k_combine_we
+    static constexpr bool PLANES_AUTO = sizeof(U) <= GMSM_PLANES_AUTO_WORDS * 4;
+    // first-level blocks per window the plane form takes (tested up to here). BN254 G1 at 2^20 - GLV half scalars, c = 16,
+    // 2^16 buckets, L = 8 - has 128; more would be a three-level plan at small L, which the cost model leaves to few windows.
+    static constexpr uint32_t PLANE_BLOCKS = 128;
 
     // Waits for the pipeline enqueued on `stream` and hands out the window totals (pinned buffer -> host_xyzz).
     static int collect_window_sums(Workspace &ws, hipStream_t stream, uint32_t nw, Ext *host_xyzz) {
@@ -170,7 +195,30 @@ struct Group : GroupHost<F_, FrP_> {
         HIP_TRY(wait_stream(stream));
         if (ws.pending_timed) StageTimer::collect(ws);
         ws.pending_timed = false;
+        if (ws.plane_np) {  // plane sums: every window's own Horner walk
+            const Ext *planes = (const Ext *)ws.pinned;
+            for (uint32_t w = 0; w < nw; ++w) {
+                const J j = fold_planes(planes + (size_t)w * ws.plane_np, 0, 1, ws.plane_log2L, ws.plane_np - 7);
+                host_xyzz[w] = j.z.is_zero() ? Ext::infinity() : xyzz_from_jac(j);
+            }
+            return GMSM_OK;
+        }
         memcpy(host_xyzz, ws.pinned, (size_t)nw * sizeof(Ext));
+        return GMSM_OK;
+    }
+    // ... and folds them: msmReduceChunk over nwin window totals, or over their plane sums
+    static int collect_folded(Workspace &ws, hipStream_t stream, unsigned c, uint32_t nwin, J *out) {
+        if (ws.plane_np) {
+            HIP_TRY(wait_stream(stream));
+            if (ws.pending_timed) StageTimer::collect(ws);
+            ws.pending_timed = false;
+            *out = fold_planes((const Ext *)ws.pinned, c, nwin, ws.plane_log2L, ws.plane_np - 7);
+            return GMSM_OK;
+        }
+        std::vector<Ext> totals(nwin);
+        int rc = collect_window_sums(ws, stream, nwin, totals.data());
+        if (rc) return rc;
+        *out = fold(totals.data(), c, nwin);
         return GMSM_OK;
     }
 
@@ -384,9 +432,11 @@ struct Group : GroupHost<F_, FrP_> {
                                    const WindowPlan &plan, hipStream_t stream, const ResidentBases *resident,
                                    void *d_out = nullptr, size_t resident_offset = 0 /* first registered base used */,
                                    bool buckets_only = false, bool time_range = false /* buckets_only: the caller collects the
-                                   stage events of this range before it enqueues the next (multiexp_device) */) {
+                                   stage events of this range before it enqueues the next (multiexp_device) */,
+                                   int tail_mode = TAIL_LADDER /* what the caller can take from ws.pinned */) {
         const uint32_t nwd = plan.nwin_local;  // windows of the digit decomposition = totals handed out
         ws.pending_timed = false;
+        ws.plane_np = 0;
         if (nwd == 0) return GMSM_OK;
         // window tables: the (window, point) pairs of all windows form ONE set of entries over one bucket set
         const bool shared = plan.shared != 0;
@@ -428,6 +478,17 @@ struct Group : GroupHost<F_, FrP_> {
         const Geometry qa = split ? plan_geometry(ctx, nw / 2, n, NB, shared) : q;  // accumulation + fix-up geometry
         const size_t tot_thr = (size_t)nw * qa.tpw;
         const size_t tot_blk = (size_t)nw * q.nblocks1;
+        // GMSM_OPT_REDUCE_TAIL: the reduction stops at its plane sums and the host fold scales them (k_plane_sums)
+        bool planes = false;
+        if constexpr (COMBINE_WE) {
+            const unsigned tail = options().reduce_tail.load(std::memory_order_relaxed);
+            const bool can = tail_mode != TAIL_LADDER && !d_out && !buckets_only && !shared && !split && q.nblocks1 <= PLANE_BLOCKS;
+            planes = can && (tail == 2 || (tail == 0 && tail_mode == TAIL_AUTO && PLANES_AUTO &&
+                                           options().reduce_shape.load(std::memory_order_relaxed) == 0));
+        }
+        uint32_t plane_h = 0;
+        while ((1u << plane_h) < q.nblocks1) ++plane_h;
+        const uint32_t plane_np = 7 + plane_h;
 
         // ---- grouping geometry
         uint32_t log2NB = 0;
@@ -471,11 +532,11 @@ struct Group : GroupHost<F_, FrP_> {
         if ((rc = ws.parted.ensure((size_t)nw * n * 4))) return rc;
         if ((rc = ws.starts.ensure((size_t)nw * (NB + 1) * 4))) return rc;
         if ((rc = ws.buckets.ensure((size_t)nw * NB * REC))) return rc;
-        if ((rc = ws.partials.ensure((tot_blk + (size_t)nw * q.nblocks2) * 2 * REC))) return rc;
+        if ((rc = ws.partials.ensure(planes ? tot_blk * 8 * REC : (tot_blk + (size_t)nw * q.nblocks2) * 2 * REC))) return rc;
         const uint32_t T = (uint32_t)(((size_t)NB + ((size_t)1 << q.log2L) - 1) >> q.log2L);  // (S, W) pairs per window of k_reduce_serial
         if ((rc = ws.red_pre.ensure((size_t)nw * T * 2 * REC))) return rc;
         if ((rc = ws.totals.ensure((size_t)nwd * sizeof(Ext)))) return rc;
-        if ((rc = ws.ensure_pinned((size_t)nwd * sizeof(Ext)))) return rc;
+        if ((rc = ws.ensure_pinned((size_t)nwd * (planes ? plane_np : 1u) * sizeof(Ext)))) return rc;
         if ((rc = ws.blockhist.ensure((size_t)nw * pchunks * nparts * 4))) return rc;
         if ((rc = ws.counts.ensure((size_t)nw * (2 * nparts + 1) * 4))) return rc;
         if ((rc = ws.seg_partials.ensure(tot_thr * 2 * REC))) return rc;
@@ -526,6 +587,12 @@ struct Group : GroupHost<F_, FrP_> {
         if constexpr (SERIAL_QUAD)
             if ((rc = ctx.allow_lds((const void *)k_reduce_serial_q<U, SERIAL_Q_QUADS>, (int)(3 * SERIAL_Q_QUADS * sizeof(QRec<U>))))) return rc;
         if ((rc = ctx.allow_lds((const void *)k_reduce2_q<U, true>, (int)(2 * RED2_TPB * sizeof(QRec<U>))))) return rc;
+        if constexpr (COMBINE_WE) {
+            if (planes) {
+                if ((rc = ctx.allow_lds((const void *)k_combine_we<U, true, true>, (int)((2 * COMBINE_N + 1) * sizeof(QRec<U>))))) return rc;
+                if ((rc = ctx.allow_lds((const void *)k_plane_sums<U, true>, (int)(PLANE_BLOCKS * sizeof(QRec<U>))))) return rc;
+            }
+        }
 
         // Stage times cover single-run calls: the ranges of a multi-range call (buckets_only) reuse a workspace's events
         // before anybody could read them, and their merges and the one reduction run on another stream - such calls are
@@ -664,7 +731,7 @@ struct Group : GroupHost<F_, FrP_> {
                                buckets_g, (const uint32_t *)cnt_g, (const LongChain *)list_g, done_g, sums_g, st_g, qa.seg);
             // ---- bucket reduction -> window totals (empty buckets are never written: the reduction consults starts[])
             if (mark) timer.mark(T_REDUCE, st);
-            if (!buckets_only) enqueue_reduce_kernels(ctx, ws, q, T, buckets_g, st_g, nk, NB, st, k0);
+            if (!buckets_only) enqueue_reduce_kernels(ctx, ws, q, T, buckets_g, st_g, nk, NB, st, k0, planes);
         };
         timer.mark(T_ACCUMULATE, stream);
         if (!split) {
@@ -688,7 +755,11 @@ struct Group : GroupHost<F_, FrP_> {
             hipLaunchKernelGGL((k_fill_infinity<Ext>), dim3((nwd - nw + 63) / 64), dim3(64), 0, stream, ws.totals.ptr, nw, nwd - nw);
         timer.mark(T_END, stream);
         HIP_TRY(hipGetLastError());
-        if (!buckets_only) {
+        if (planes) {  // k_plane_sums wrote ws.pinned itself: nothing to copy
+            ws.plane_np = plane_np;
+            ws.plane_log2L = q.log2L;
+            g_plane_runs.fetch_add(1, std::memory_order_relaxed);
+        } else if (!buckets_only) {
             if (d_out)
                 HIP_TRY(hipMemcpyAsync(d_out, ws.totals.ptr, (size_t)nwd * sizeof(Ext), hipMemcpyDeviceToDevice, stream));
             else
@@ -722,7 +793,8 @@ struct Group : GroupHost<F_, FrP_> {
     // stored, infinity as zz = 0) -> ws.totals. Scratch: ws.red_pre, ws.partials.
     static void enqueue_reduce_kernels(Context &ctx, Workspace &ws, const Geometry &q, uint32_t T, const void *buckets,
                                        const uint32_t *starts, uint32_t nw, uint32_t NB, hipStream_t stream,
-                                       uint32_t k0 = 0 /* first window of a group: offsets into the scratch and the totals */) {
+                                       uint32_t k0 = 0 /* first window of a group: offsets into the scratch and the totals */,
+                                       bool planes = false /* stop at the plane sums, written to ws.pinned (k0 == 0) */) {
         constexpr size_t RECB = sizeof(typename OpsSerial::Mem);
         void *red_pre = (char *)ws.red_pre.ptr + (size_t)k0 * T * 2 * RECB;
         void *partials = (char *)ws.partials.ptr + (size_t)k0 * q.nblocks1 * 2 * RECB;  // (groups only with two levels)
@@ -736,6 +808,18 @@ struct Group : GroupHost<F_, FrP_> {
         else
             hipLaunchKernelGGL((k_reduce_serial<OpsSerial>), dim3((T + 255) / 256, nw), dim3(256), 0, stream, buckets, NB,
                                q.log2L, T, starts, red_pre);
+        if constexpr (COMBINE_WE) {
+            if (planes) {  // GMSM_OPT_REDUCE_TAIL: sums only, the host fold applies the weights (fold_planes)
+                uint32_t h = 0;
+                while ((1u << h) < q.nblocks1) ++h;
+                const uint32_t quads = std::min(64u, std::max(16u, (1u << h) / 2));  // a step has at most 2^h / 2 additions
+                hipLaunchKernelGGL((k_combine_we<U, true, true>), dim3(q.nblocks1, nw), dim3(4 * COMBINE_N),
+                                   (2 * COMBINE_N + 1) * sizeof(QRec<U>), stream, q.log2L, ws.partials.ptr, 0u, (const void *)red_pre, T);
+                hipLaunchKernelGGL((k_plane_sums<U, true>), dim3(nw, 8), dim3(4 * quads), ((size_t)1 << h) * sizeof(QRec<U>), stream,
+                                   (const void *)ws.partials.ptr, q.nblocks1, h, ws.pinned);
+                return;
+            }
+        }
         // one combine level: `pairs` (S, W) pairs per window, each the sum of 2^l2 buckets (S prescaled by the caller's
         // factor when l2 == 0) -> `blocks` pairs per window
         const auto combine = [&](const void *in, uint32_t pairs, void *out, uint32_t blocks, uint32_t l2, uint32_t pre) {
@@ -778,6 +862,7 @@ struct Group : GroupHost<F_, FrP_> {
         const Geometry q = plan_geometry(ctx, nw, n_for_geometry, NB);
         const uint32_t T = (uint32_t)(((size_t)NB + ((size_t)1 << q.log2L) - 1) >> q.log2L);
         int rc;
+        ws.plane_np = 0;
         if ((rc = ws.partials.ensure((size_t)nw * (q.nblocks1 + q.nblocks2) * 2 * REC))) return rc;
         if ((rc = ws.red_pre.ensure((size_t)nw * T * 2 * REC))) return rc;
         if ((rc = ws.totals.ensure((size_t)nwd * sizeof(Ext)))) return rc;
@@ -1312,6 +1397,7 @@ struct Group : GroupHost<F_, FrP_> {
         constexpr size_t REC = sizeof(typename OpsSerial::Mem);
         int rc;
         ws.pending_timed = false;
+        ws.plane_np = 0;
         if ((rc = begin_use(ws, ws.stream))) return rc;
         if ((rc = ws.ensure_pinned((size_t)plan.nwin_total * sizeof(Ext)))) return rc;
         if ((rc = ws.small_sums.ensure((size_t)nw * sp.nslices * REC))) return rc;
@@ -1404,13 +1490,8 @@ struct Group : GroupHost<F_, FrP_> {
         const WindowPlan plan = plan_for(resident, n);
         const unsigned c = plan.c;
         const unsigned nr = device_ranges(n, plan);
+        if (nr <= 1) return window_sums_folded(ctx, ws, d_points, d_scalars, n, plan, caller_stream, out, resident);
         std::vector<Ext> totals(plan.nwin_total);
-        if (nr <= 1) {
-            int rc = window_sums(ctx, ws, d_points, d_scalars, n, plan, caller_stream, totals.data(), resident);
-            if (rc) return rc;
-            *out = fold(totals.data(), c, plan.nwin_total);
-            return GMSM_OK;
-        }
         // Consecutive point ranges on the workspace's stream: each leaves its bucket sums, k_merge_buckets adds them to the
         // running buckets, one reduction at the end (the reference's split + AddAssign, multiexp.go:98-140, bucket by bucket).
         constexpr size_t REC = sizeof(typename OpsSerial::Mem);
@@ -1452,18 +1533,14 @@ struct Group : GroupHost<F_, FrP_> {
         WindowPlan plan = plan_for(resident, n);
         if (n > max_run_points(plan)) plan = make_plan(choose_c(FR_BITS, AFF_BYTES, n), 0, 1);  // one run per ticket: plain path
         const unsigned c = plan.c;
-        int rc = enqueue_window_sums(ctx, ws, nullptr, d_scalars, n, plan, ws.stream, resident);
+        int rc = enqueue_window_sums(ctx, ws, nullptr, d_scalars, n, plan, ws.stream, resident, nullptr, 0, false, false, TAIL_AUTO);
         if (rc) return rc;
         ws.pending_c = c;
         ws.pending_nw = plan.nwin_total;
         return GMSM_OK;
     }
     static int multiexp_collect(Workspace &ws, J *out) {
-        std::vector<Ext> totals(ws.pending_nw);
-        int rc = collect_window_sums(ws, ws.stream, ws.pending_nw, totals.data());
-        if (rc) return rc;
-        *out = fold(totals.data(), ws.pending_c);
-        return GMSM_OK;
+        return collect_folded(ws, ws.stream, ws.pending_c, ws.pending_nw, out);
     }
 
 

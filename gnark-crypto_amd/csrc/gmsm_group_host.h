@@ -51,6 +51,48 @@ struct GroupHost {
         return acc;
     }
 
+    // The fold when the device stops its reduction where the sums end (GMSM_OPT_REDUCE_TAIL, k_plane_sums): window w comes as
+    // 7 + nhigh planes [Wsum, m_0..m_5, h_0..h_(nhigh-1)] with
+    //   total_w = Wsum + sum_l 2^(log2L + l) m_l + sum_l 2^(log2L + 6 + l) h_l,   MSM = sum_w 2^(c w) total_w:
+    // ONE Horner walk from the top bit down, every plane added at its bit position, planes at infinity skipped. Planes arrive
+    // at most bit positions of a window, so the running sum stays in the extended form (9 products per doubling, 14 per
+    // addition) and changes to Jacobian coordinates (7 per doubling, 6 for the change there and back) only for runs of four
+    // or more doublings. nwin = 1 gives one window's total (c unused).
+    static J fold_planes(const Ext *planes, unsigned c, unsigned nwin, unsigned log2L, unsigned nhigh) {
+        const unsigned NP = 7 + nhigh;
+        const unsigned top = c * (nwin - 1) + log2L + NP - 2;
+        std::vector<int> head(top + 1, -1), next((size_t)nwin * NP, -1);
+        for (unsigned w = 0; w < nwin; ++w)
+            for (unsigned i = 0; i < NP; ++i) {
+                const int idx = (int)(w * NP + i);
+                if (planes[idx].zz.is_zero()) continue;
+                const unsigned b = c * w + (i == 0 ? 0 : log2L + i - 1);
+                next[idx] = head[b];
+                head[b] = idx;
+            }
+        int b = (int)top;
+        while (b >= 0 && head[b] < 0) --b;
+        Ext acc = Ext::infinity();
+        while (b >= 0) {
+            for (int i = head[b]; i >= 0; i = next[i]) xyzz_add(acc, planes[i]);
+            if (b == 0) break;
+            int nb = b - 1;  // the next bit position with planes, or the last one
+            while (nb > 0 && head[nb] < 0) --nb;
+            const int gap = b - nb;
+            if (!acc.zz.is_zero()) {
+                if (gap >= 4) {
+                    J j = jac_from_xyzz(acc);
+                    for (int l = 0; l < gap; ++l) j = jac_double(j);
+                    acc = j.z.is_zero() ? Ext::infinity() : xyzz_from_jac(j);
+                } else {
+                    for (int l = 0; l < gap; ++l) acc = xyzz_double(acc);
+                }
+            }
+            b = nb;
+        }
+        return jac_from_xyzz(acc);
+    }
+
     // out[i] = [k0 + i*k1] base for i < n (affine). Host-side, multi-threaded: start point by double-and-add, then
     // repeated mixed addition of step = [k1]base with block-wise batch normalisation (one inversion per block).
     // Utility for building SRS-like on-curve bases (cf. BatchScalarMultiplicationG1, ecc/bn254/g1.go:1039, and the

@@ -171,6 +171,10 @@ struct VTableOf {
         *c = p.c, *nwin = p.nwin_total, *entries_per_point = p.glv ? 2u : 1u, *fused = 0u;
     }
     static void reduce_shape(const Context &ctx, uint32_t nw, uint32_t nbuckets, uint32_t out[6]) { G::reduce_shape(ctx, nw, nbuckets, out); }
+    static void fold_planes(const uint64_t *planes, unsigned c, unsigned nwin, unsigned log2L, unsigned nhigh, uint64_t *out_jac) {
+        typename G::J j = G::fold_planes(reinterpret_cast<const typename G::Ext *>(planes), c, nwin, log2L, nhigh);
+        memcpy(out_jac, &j, sizeof j);
+    }
     static int debug_field_op(int field, int op, const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out) {
         using BaseP = typename G::F::Params;
         if (field == 0) {
@@ -626,7 +630,7 @@ struct VTableOf {
             GMSM_VT(decode_raw), GMSM_VT(validate_points), GMSM_VT(decode_compressed), GMSM_VT(encode_compressed);
             GMSM_VT(fft_domain_new), GMSM_VT(fft_run), GMSM_VT(fft_bit_reverse);
             GMSM_VT(precompute_tables), GMSM_VT(tables_serve), GMSM_VT(shard_piece), GMSM_VT(host_piece_ranges);
-            GMSM_VT(debug_glv_split), GMSM_VT(plan_info), GMSM_VT(reduce_shape);
+            GMSM_VT(debug_glv_split), GMSM_VT(plan_info), GMSM_VT(reduce_shape), GMSM_VT(fold_planes);
             GMSM_VT(poly_eval), GMSM_VT(poly_div), GMSM_VT(kzg_open);
             if constexpr (IS_G1) GMSM_VT(to_lagrange);  // the three G1-only members stay null for the G2 groups
             GMSM_VT(fflonk_next_divisor), GMSM_VT(open_check), GMSM_VT(fflonk_fold);

@@ -384,7 +384,10 @@ __global__ void __launch_bounds__(4 * N) k_combine_q(uint32_t log2L, void *__res
 // while quad 15 doubles the parked A log2span times. 17 steps at L = 8 (k_combine_q: 16), about half the issue work: for
 // the element types whose combine is throughput-bound (several workgroups per CU: the 9- and 14-limb fields).
 // tests/test_combine_model.py runs this step machine over Z. Launch and LDS as k_combine_q<U, INL, 64>.
-template <class U, bool INL>
+// PLANES (GMSM_OPT_REDUCE_TAIL, host planes): the kernel stops where the sums end - no tail program, no parked doubler - and
+// stores 8 records per block: A, M_0..M_5, sum W (out1[(k * nblocks1 + blk) * 8 + 0..7]; log2L and prescale are unused).
+// k_plane_sums adds them up over the blocks of a window and the host fold applies the weights (Group::fold_planes).
+template <class U, bool INL, bool PLANES = false>
 __global__ void __launch_bounds__(256) k_combine_we(uint32_t log2L, void *__restrict__ out1, uint32_t prescale,
                                                     const void *__restrict__ pre, uint32_t T) {
     constexpr uint32_t N = 64;
@@ -416,6 +419,13 @@ __global__ void __launch_bounds__(256) k_combine_we(uint32_t log2L, void *__rest
         __syncthreads();
         quad_add_store<U, INL>(X, o, act, lane);
         __syncthreads();
+    }
+    if constexpr (PLANES) {
+        if (j < 8) {
+            const QRec<U> *src = j == 0 ? &S[0] : j < 7 ? &S[1u << (j - 1)] : &W[0];
+            quad_rec_store<U>(out1, ((size_t)k * gridDim.x + blk) * 8 + j, src, lane);
+        }
+        return;
     }
     if (j == 0) {  // park A = S[0] for the prescaling doubler
         PARK->c[t & 3u] = S[0].c[t & 3u];
@@ -450,6 +460,72 @@ __global__ void __launch_bounds__(256) k_combine_we(uint32_t log2L, void *__rest
     }
     if (j == 0) quad_rec_store<U>(out1, ((size_t)k * gridDim.x + blk) * 2 + 1, &W[0], lane);
     if (j == 1) quad_rec_store<U>(out1, ((size_t)k * gridDim.x + blk) * 2 + 0, PARK, lane);
+}
+
+// ------------------------------------------------------------------ plane sums (reduction tail on the host)
+// k_combine_we<PLANES> has left, per block of a window, A_blk, M_0..M_5 and sum W. With t = 64 blk + t' the window total is
+//   sum W + L sum_t t S_t = Wsum + sum_l 2^(log2L + l) m_l + sum_l 2^(log2L + 6 + l) h_l,
+// m_l = sum_blk M_l(blk), Wsum = sum_blk sumW(blk), h_l = the sum of the A_blk whose index has bit l set: additions only.
+// One workgroup per (window, plane p): p = 0 the A_blk, 1..6 the M_l, 7 sum W; slot b holds the plane's record of block b,
+// NBP = 2^H >= nblocks1 slots (absent blocks are infinity). Step s = 1..H, g = NBP >> s: a carried plane (p >= 1) halves
+// (slot i += slot i + g: g additions); plane 0 runs the pair-sum pyramid and the trees over its odd elements exactly as
+// k_combine_we does over the S_t (g s additions: at most NBP / 2 in every step). Then the carried plane's quad 0 converts
+// slot 0 - plane 0's quads l < H convert h_l = slot 1 << l - to canonical saturated XYZZ (infinity = (1, 1, 0, 0)) and stores
+// it into `planes_out`, the workspace's mapped pinned buffer, [window][7 + H] = Wsum, m_0..m_5, h_0..h_(H-1): no copy
+// kernel follows. The device doubles nothing. (One workgroup per window - 1136 additions of a window on one compute unit -
+// took 71 us at 128 blocks; the planes are independent.)
+// grid = (nwin_local, 8), block = 4 * quads (a multiple of 64), dynamic LDS = (1 << H) * sizeof(QRec<U>).
+template <class U, bool INL>
+__global__ void __launch_bounds__(256) k_plane_sums(const void *__restrict__ in1, uint32_t nblocks1, uint32_t H,
+                                                    void *__restrict__ planes_out) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    QRec<U> *P = reinterpret_cast<QRec<U> *>(lds_raw);
+    const uint32_t NBP = 1u << H, k = blockIdx.x, p = blockIdx.y, t = threadIdx.x, j = t >> 2, lane = t & 63u, nq = blockDim.x >> 2;
+    for (uint32_t b = j; b < NBP; b += nq) quad_rec_load<U>(&P[b], in1, ((size_t)k * nblocks1 + b) * 8 + p, b < nblocks1, lane);
+    __syncthreads();
+#pragma nounroll
+    for (uint32_t s = 1; s <= H; ++s) {
+        const uint32_t g = NBP >> s, nops = p ? g : g * s;
+#pragma nounroll
+        for (uint32_t o0 = 0; o0 < nops; o0 += nq) {
+            const uint32_t op = o0 + j;
+            const bool act = op < nops;
+            QRec<U> *X = &P[0], *Y = &P[0];
+            if (act) {
+                const uint32_t G = op >> (H - s), i = op & (g - 1u);
+                if (p) {  // carried plane: halving tree (G == 0)
+                    X = &P[i];
+                    Y = X + g;
+                } else if (G == 0u) {  // pair sums of level l = s - 1
+                    const uint32_t l = s - 1;
+                    X = &P[(2 * i) << l];
+                    Y = &P[(2 * i + 1) << l];
+                } else {  // tree over the odd elements of level l = G - 1 < s - 1
+                    const uint32_t l = G - 1u;
+                    X = &P[(2 * i + 1) << l];
+                    Y = &P[(2 * (i + g) + 1) << l];
+                }
+            }
+            const QAddOps<U> o = quad_add_load<U>(X, Y, lane);
+            __syncthreads();
+            quad_add_store<U, INL>(X, o, act, lane);
+            __syncthreads();
+        }
+    }
+    using T = LzTraits<U>;
+    using Mem = XYZZ<typename T::Sat>;
+    const uint32_t NP = 7u + H, r = t & 3u, nres = p ? 1u : H;
+    for (uint32_t q = j; q < nres; q += nq) {
+        const QRec<U> *src = p ? &P[0] : &P[1u << q];
+        const uint32_t slot = p == 7u ? 0u : p ? p : 7u + q;
+        typename T::Sat *dst = reinterpret_cast<typename T::Sat *>(reinterpret_cast<char *>(planes_out) + ((size_t)k * NP + slot) * sizeof(Mem));
+        typename T::Sat v = T::template to_sat<INL>(src->c[r]);
+        if (src->inf) {
+            const Mem inf = Mem::infinity();
+            v = r == 0 ? inf.x : r == 1 ? inf.y : r == 2 ? inf.zz : inf.zzz;
+        }
+        dst[r] = v;
+    }
 }
 
 #endif  // __HIPCC__

@@ -414,6 +414,16 @@ class _Group:
             raise RuntimeError(self._error(rc))
         return out
 
+    def fold_planes(self, planes, c, nwin, log2L, nblocks1):
+        """gmsm_debug_fold_planes: the host fold over nwin x (7 + ceil(log2 nblocks1)) plane sums (GMSM_OPT_REDUCE_TAIL = 2)."""
+        planes = np.ascontiguousarray(planes, dtype=np.uint64)
+        assert planes.size == nwin * (7 + (nblocks1 - 1).bit_length()) * self.xyzz_limbs
+        out = np.zeros(self.jac_limbs, dtype=np.uint64)
+        rc = _lib.load().gmsm_debug_fold_planes(self.gid, c, nwin, log2L, nblocks1, _ptr(planes), _ptr(out))
+        if rc:
+            raise RuntimeError(self._error(rc))
+        return out
+
     def jac_to_affine(self, jac):
         L = _lib.load()
         jac = np.ascontiguousarray(jac, dtype=np.uint64)

@@ -513,6 +513,12 @@ int gmsm_debug_group_op(int group, int op, const uint64_t *acc, const uint64_t *
  * current options: out = {log2L, level-1 workgroups per set, workgroups of the second combine (0 = two levels), the combine
  * kernel of level 1 (1 k_combine_q, 2 k_combine_we), the serial kernel (0 one lane, 1 lane quads), the quads of k_reduce2_q} */
 int gmsm_debug_reduce_shape(int group, uint32_t nw, uint32_t nbuckets, uint32_t out[6]);
+/* the host fold over the plane sums of k_plane_sums (GMSM_OPT_REDUCE_TAIL = 2), no device needed: planes = nwin x
+ * (7 + ceil(log2 nblocks1)) XYZZ values per window {Wsum, m_0..m_5, h_0..}; out_jac = sum_w 2^(c w) (Wsum_w +
+ * sum_l 2^(log2L + l) m_l + sum_l 2^(log2L + 6 + l) h_l), infinity as (1, 1, 0) */
+int gmsm_debug_fold_planes(int group, unsigned c, unsigned nwin, unsigned log2L, unsigned nblocks1, const uint64_t *planes,
+                           uint64_t *out_jac);
+unsigned long gmsm_debug_plane_runs(void); /* pipeline runs whose reduction ended in k_plane_sums so far (tests) */
 
 /* ---- utilities ---- */
 /* out_points[i] = [k0 + i*k1] * base, i < n (affine, Go layout). k0,k1: plain (non-Montgomery) little-endian limbs.
@@ -572,6 +578,16 @@ enum gmsm_option {
                                  carry pass's lanes of several tiles at 2^16 coefficients instead of 2^21). Cost only: every
                                  output is the same field element. Read once per call. The prefix products and the batch inversion
                                  behind gmsm_fr_batch_invert and the gmsm_iop_ratio entries cut their vectors the same way. */
+    GMSM_OPT_REDUCE_TAIL = 13, /* who applies the weights at the end of the bucket reduction. 1 = the device: the doubling ladders of
+                                 k_combine_we / k_combine_q and k_reduce2_q leave one total per window, the host folds the windows.
+                                 2 = the host: the device stops where its wide sums end (k_combine_we without its tail, then
+                                 k_plane_sums: additions only, 7 + ceil(log2 blocks) sums per window written straight into the pinned
+                                 result buffer) and the host fold adds every sum at its bit position in one Horner walk - where the
+                                 shape allows it (a group that has k_combine_we, at most 128 first-level blocks, the result collected
+                                 on the host: not gmsm_window_sums_enqueue, merged point ranges, window tables or the sharded
+                                 exchange; the ladder elsewhere). 0 (default) = 2 for the MultiExp entries of the groups where it was
+                                 measured ahead (BN254 G1) unless GMSM_OPT_REDUCE_SHAPE forces a shape, 1 elsewhere. Cost only: every
+                                 result is the same group element. gmsm_debug_plane_runs counts the runs that took the host form. */
     GMSM_OPT_REDUCE_SHAPE = 12 /* for the tests of the bucket reduction's launch shapes: 0 (default) = the cost model. A packed value:
                                  bits 0-3 log2L (1..8 buckets per serial segment as a power of two, 0 = model), bits 4-5 the levels
                                  (2 = serial, combine, level 2; 3 = a second combine in between; 0 = model), bits 6-7 the combine kernel
