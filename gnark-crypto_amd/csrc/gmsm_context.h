@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <condition_variable>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -136,12 +137,20 @@ struct FftDomain {
     DeviceBuffer coset, coset_inv_scaled;       // u^i and u^-i / n for i < n (lazy domain), built by the first coset transform
     std::vector<uint64_t> cardinality_inv_lz;   // 1/n, lazy domain
     bool coset_ready = false;
+    // 1/(X^n - 1) on this domain's coset for a small domain of 2^key elements (iop.DivideByXMinusOne, gmsm_iop_poly.h):
+    // cardinality / n canonical elements, built by the first quotient over that pair of domains, under mu
+    struct XnInv {
+        DeviceBuffer table;
+        bool ready = false;
+    };
+    std::map<unsigned, XnInv> xn_inv;
     std::mutex mu;                            // serialises the lazy coset build and transforms that share the tables
     FftDomain() = default;
     FftDomain(const FftDomain &) = delete;
     FftDomain &operator=(const FftDomain &) = delete;
     ~FftDomain() {
-        DeviceBuffer *bufs[] = {&twiddles_lz, &twiddles_inv_lz, &twiddles_rev_lz, &twiddles_inv_rev_lz, &coset, &coset_inv_scaled};
+        std::vector<DeviceBuffer *> bufs = {&twiddles_lz, &twiddles_inv_lz, &twiddles_rev_lz, &twiddles_inv_rev_lz, &coset, &coset_inv_scaled};
+        for (auto &e : xn_inv) bufs.push_back(&e.second.table);
         bool any = false;
         for (auto *b : bufs) any = any || b->ptr;
         if (!any) return;
@@ -786,6 +795,18 @@ struct GroupVTable {
     int (*ratio_shuffled)(Context &ctx, FftDomain *d, const uint64_t *num, const void *d_num, const uint64_t *den, const void *d_den,
                           size_t m, const uint32_t *num_layouts, const uint32_t *den_layouts, const uint64_t *beta, int basis, int layout,
                           hipStream_t stream, uint64_t *out, void *d_out);
+    // iop.Polynomial over the group's scalar field (gmsm_iop_poly.h); nullptr for the G2 groups, as above. The engine has
+    // checked every argument: values of basis / layout, powers of two, the field's 2-adicity, overlaps.
+    //   iop_to_basis: in place on a (host) / d_a (device), cardinality elements of which the first len are given
+    //   iop_evaluate: k polynomials of len elements, concatenated; shift in 0..5; coset given when basis is LagrangeCoset
+    //   iop_quotient: DivideByXMinusOne of the card(big) elements of a; shift already reduced mod card(small)
+    int (*iop_to_basis)(Context &ctx, FftDomain *d, uint64_t *a, void *d_a, size_t len, int basis, int layout, int to_basis, hipStream_t stream,
+                        int *out_layout);
+    int (*iop_evaluate)(Context &ctx, const uint64_t *polys, const void *d_polys, size_t k, size_t len, size_t size, int basis,
+                        const uint32_t *layouts, unsigned shift, const uint64_t *coset, const uint64_t *x, hipStream_t stream,
+                        uint64_t *out_values);
+    int (*iop_quotient)(Context &ctx, FftDomain *small, FftDomain *big, const uint64_t *a, const void *d_a, int layout, size_t shift,
+                        hipStream_t stream, uint64_t *out, void *d_out);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

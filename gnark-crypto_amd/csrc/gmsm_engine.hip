@@ -1724,6 +1724,87 @@ GMSM_EXPORT int gmsm_iop_ratio_shuffled(uint64_t domain, const uint64_t *num, co
                               d_out);
 }
 
+// ------------------------------------------------------------------ iop.Polynomial: basis changes, Evaluate, DivideByXMinusOne (gmsm_iop_poly.h)
+// Checks in the order of the ratio entries: what needs nothing but the arguments, then the domain handles, then what needs
+// their cardinalities.
+static int iop_basis(const char *E, const char *name, int basis) {
+    if (basis != 1 && basis != 2 && basis != 4)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": unknown " + name + " " + std::to_string(basis) + " (1 Canonical, 2 Lagrange, 4 LagrangeCoset)");
+    return GMSM_OK;
+}
+static int iop_layout(const char *E, int layout) {
+    if (layout != 8 && layout != 16)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": unknown layout " + std::to_string(layout) + " (8 Regular, 16 BitReverse)");
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_iop_to_basis(uint64_t domain, uint64_t *a, void *d_a, size_t len, int basis, int layout, int to_basis, void *hip_stream,
+                                  int *out_layout) {
+    const char *E = "gmsm_iop_to_basis";
+    int rc = ratio_pair(E, "a", "d_a", a, d_a);
+    if (rc || (rc = iop_basis(E, "basis", basis)) || (rc = iop_layout(E, layout)) || (rc = iop_basis(E, "to_basis", to_basis))) return rc;
+    if (!out_layout) return fail(GMSM_ERR_ARG, std::string(E) + ": out_layout is null");
+    FftRef d = g_fft.get(domain);
+    if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
+    if (len > ((size_t)1 << d->log2n))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": len " + std::to_string(len) + " is larger than the domain's cardinality");
+    const GroupVTable *vt = fr_vtable(d->group);
+    Context *ctx;
+    if ((rc = enter_on(d->device, &ctx))) return rc;  // the domain decides the device
+    if ((rc = check_device_vector(E, "d_a", d_a, ctx->device))) return rc;
+    return vt->iop_to_basis(*ctx, d.get(), a, d_a, len, basis, layout, to_basis, (hipStream_t)hip_stream, out_layout);
+}
+
+GMSM_EXPORT int gmsm_iop_evaluate(int group, const uint64_t *polys, const void *d_polys, size_t k, size_t len, size_t size, int basis,
+                                  const uint32_t *layouts, unsigned shift, const uint64_t *coset, const uint64_t *x, void *hip_stream,
+                                  uint64_t *out_values) {
+    const GroupVTable *vt = fr_vtable(group);
+    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    const char *E = "gmsm_iop_evaluate";
+    if (k == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": no polynomial (k == 0)");
+    if (len == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": empty polynomial (len == 0)");
+    if (size == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": size == 0");
+    int rc = iop_basis(E, "basis", basis);
+    if (rc || (rc = ratio_layouts(E, "layouts", layouts, k)) || (rc = ratio_pair(E, "polys", "d_polys", polys, d_polys))) return rc;
+    if (!x || !out_values) return fail(GMSM_ERR_ARG, std::string(E) + ": x and out_values must not be null");
+    if (basis == 4 && !coset) return fail(GMSM_ERR_ARG, std::string(E) + ": coset is null and the basis is LagrangeCoset");
+    if (shift > 5)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": shift " + std::to_string(shift) + " is outside 0..5 (the reference evaluates at 0 there)");
+    bool reversed = false;
+    for (size_t j = 0; j < k; ++j) reversed = reversed || layouts[j] == 16;
+    if ((basis != 1 || reversed) && (len & (len - 1)))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": len must be a power of 2 in a Lagrange basis or a BitReverse layout");
+    if (basis != 1 && len > ((size_t)1 << vt->fr_max_order)) return fail(GMSM_ERR_ARG, ERR_ROOT);
+    if (shift && size > ((size_t)1 << vt->fr_max_order)) return fail(GMSM_ERR_ARG, ERR_ROOT);  // fft.Generator(size)
+    if (k > (((size_t)1 << 62) / len)) return fail(GMSM_ERR_ARG, std::string(E) + ": k * len does not fit");
+    if (polys && ratio_overlap(out_values, nullptr, k * vt->scalar_bytes, polys, nullptr, k * len * vt->scalar_bytes)) return ratio_aliases(E);
+    Context *ctx;
+    if ((rc = enter_owner(d_polys, &ctx))) return rc;
+    if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device))) return rc;
+    return vt->iop_evaluate(*ctx, polys, d_polys, k, len, size, basis, layouts, shift, coset, x, (hipStream_t)hip_stream, out_values);
+}
+
+GMSM_EXPORT int gmsm_iop_divide_by_x_minus_one(uint64_t domain_small, uint64_t domain_big, const uint64_t *a, const void *d_a, int basis,
+                                               int layout, uint64_t shift, void *hip_stream, uint64_t *out, void *d_out) {
+    const char *E = "gmsm_iop_divide_by_x_minus_one";
+    int rc = ratio_pair(E, "a", "d_a", a, d_a);
+    if (rc || (rc = ratio_pair(E, "out", "d_out", out, d_out)) || (rc = iop_basis(E, "basis", basis))) return rc;
+    if (basis != 4) return fail(GMSM_ERR_ARG, "the basis must be LagrangeCoset");  // ErrMustBeLagrangeCoset
+    if ((rc = iop_layout(E, layout))) return rc;
+    FftRef small = g_fft.get(domain_small), big = g_fft.get(domain_big);
+    if (!small || !big) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
+    if ((small->group & ~1) != (big->group & ~1)) return fail(GMSM_ERR_ARG, std::string(E) + ": the two domains are of different curves");
+    if (small->log2n > big->log2n) return fail(GMSM_ERR_ARG, std::string(E) + ": the small domain is larger than the big one");
+    const GroupVTable *vt = fr_vtable(big->group);
+    const size_t bytes = vt->scalar_bytes << big->log2n;
+    if (ratio_overlap(out, d_out, bytes, a, d_a, bytes)) return ratio_aliases(E);
+    Context *ctx;
+    if ((rc = enter_on(big->device, &ctx))) return rc;  // the big domain decides the device
+    if ((rc = check_device_vector(E, "d_a", d_a, ctx->device)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
+    return vt->iop_quotient(*ctx, small.get(), big.get(), a, d_a, layout, (size_t)(shift & (((uint64_t)1 << small->log2n) - 1)),
+                            (hipStream_t)hip_stream, out, d_out);
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {

@@ -25,6 +25,7 @@
 #include "gmsm_group_fft.h"
 #include "gmsm_scale.h"
 #include "gmsm_ratio.h"
+#include "gmsm_iop_poly.h"
 
 namespace gmsm {
 

@@ -613,6 +613,87 @@ struct VTableOf {
         HIP_TRY(hipGetLastError());
         return ratio_finish(ws, timer, d, b, n, basis, layout, out, d_out, nullptr, nullptr);
     }
+    // ---- iop.Polynomial: basis changes, Evaluate, DivideByXMinusOne (gmsm_iop_poly.h); in the G1 tables only, like the ratios
+    using IP = IopPolyField<typename G::FrP>;
+    static int iop_to_basis(Context &ctx, FftDomain *d, uint64_t *a, void *d_a, size_t len, int basis, int layout, int to_basis,
+                            hipStream_t caller, int *out_layout) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const size_t n = (size_t)1 << d->log2n;
+        Fr *v = (Fr *)d_a;
+        int rc;
+        DrainOnExit drain{ws.stream};
+        if (a) {
+            if ((rc = ws.h2d_scalars.ensure(n * sizeof(Fr)))) return rc;
+            v = (Fr *)ws.h2d_scalars.ptr;
+            if (len) HIP_TRY(hipMemcpyAsync(v, a, len * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+        } else if ((rc = order_after(ws, caller))) {
+            return rc;
+        }
+        // grow (polynomial.go:351-356): the tail is zero whatever the layout, also when the basis is already the target
+        if (len < n) HIP_TRY(hipMemsetAsync(v + len, 0, (n - len) * sizeof(Fr), ws.stream));
+        {
+            std::lock_guard<std::mutex> lk(d->mu);
+            rc = IP::to_basis(ws.stream, d, v, basis, layout, to_basis, out_layout);
+        }
+        if (rc) return rc;
+        if (a) HIP_TRY(hipMemcpyAsync(a, v, n * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    static int iop_evaluate(Context &ctx, const uint64_t *polys, const void *d_polys, size_t k, size_t len, size_t size, int basis,
+                            const uint32_t *layouts, unsigned shift, const uint64_t *coset, const uint64_t *x, hipStream_t caller,
+                            uint64_t *out_values) {
+        const Fr xx = IP::effective_point(x, basis, coset, shift, size);
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const Fr *in;
+        int rc = poly_input(ws, polys, d_polys, k * len, caller, &in);
+        if (rc) return rc;
+        const unsigned lanes = PF::lane_option();
+        DrainOnExit drain{ws.stream};
+        Fr *vals;
+        if (basis == IOP_CANONICAL) {
+            if ((rc = ws.poly.ensure((k + PF::scratch_elems(len, lanes)) * sizeof(Fr)))) return rc;
+            vals = (Fr *)ws.poly.ptr;
+            const FftPowers<typename G::FrP> pw = FftField<typename G::FrP>::powers_of(xx);
+            for (size_t j = 0; j < k; ++j)
+                if ((rc = IP::eval_canonical(ws.stream, pw, in + j * len, len, layouts[j] == IOP_BIT_REVERSE, vals + j, vals + k, lanes))) return rc;
+        } else {
+            unsigned log2len = 0;
+            while (((size_t)1 << log2len) < len) ++log2len;
+            const size_t part = IP::bary_scratch(k, len, lanes);
+            if ((rc = ws.poly.ensure((k + part + word_slots((k + 1) / 2)) * sizeof(Fr)))) return rc;
+            vals = (Fr *)ws.poly.ptr;
+            uint32_t *lay = (uint32_t *)(vals + k + part);
+            HIP_TRY(hipMemcpyAsync(lay, layouts, k * sizeof(uint32_t), hipMemcpyHostToDevice, ws.stream));
+            if ((rc = IP::barycentric(ws.stream, in, (const uint32_t *)lay, k, len, log2len, xx, vals + k, vals, lanes))) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(out_values, vals, k * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    static int iop_quotient(Context &ctx, FftDomain *small, FftDomain *big, const uint64_t *a, const void *d_a, int layout, size_t shift,
+                            hipStream_t caller, uint64_t *out, void *d_out) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        const size_t N = (size_t)1 << big->log2n, rho = N >> small->log2n;
+        const Fr *in;
+        int rc = poly_input(ws, a, d_a, N, caller, &in);
+        if (rc) return rc;
+        if (d_out && a && (rc = order_after(ws, caller))) return rc;  // the caller's stream may still use d_out
+        if ((rc = ws.poly.ensure((rho + (out ? N : 0)) * sizeof(Fr)))) return rc;
+        Fr *run = (Fr *)ws.poly.ptr, *res = out ? run + rho : (Fr *)d_out;
+        DrainOnExit drain{ws.stream};
+        {
+            std::lock_guard<std::mutex> lk(big->mu);
+            rc = IP::quotient(ws.stream, big, small->log2n, in, layout == (int)IOP_BIT_REVERSE, shift * rho, run, res, PF::lane_option());
+        }
+        if (rc) return rc;
+        if (out) HIP_TRY(hipMemcpyAsync(out, res, N * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
     static const GroupVTable *get() {
         // Filled by name: several members have the same type (decode_raw / decode_compressed, fold / jac_to_affine), so a
         // positional list with two of them swapped would compile.
@@ -637,6 +718,7 @@ struct VTableOf {
             if constexpr (IS_G1) GMSM_VT(open_w), GMSM_VT(open_wprime);
             GMSM_VT(batch_scale), GMSM_VT(linear_combinations);
             if constexpr (IS_G1) GMSM_VT(fr_batch_invert), GMSM_VT(ratio_copy), GMSM_VT(ratio_shuffled);
+            if constexpr (IS_G1) GMSM_VT(iop_to_basis), GMSM_VT(iop_evaluate), GMSM_VT(iop_quotient);
 #undef GMSM_VT
             return v;
         }();

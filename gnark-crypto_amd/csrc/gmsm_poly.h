@@ -31,36 +31,45 @@ namespace gmsm {
 constexpr unsigned POLY_TPB = 256;  // lanes per tile
 constexpr unsigned POLY_LOG_TPB = 8;
 
+// where coefficient i of a vector of m sits: i, or with REV its bit reversal (m a power of two: a BitReverse layout of package
+// iop, gmsm_iop_poly.h)
+template <int REV>
+__device__ __forceinline__ size_t poly_index(size_t i, size_t m) {
+    if (REV) return fft_bitrev(i, 63u - (unsigned)__clzll((unsigned long long)m));
+    return i;
+}
+
 // Horner over lane g's coefficients [g T, g T + T) of v (zero beyond m), base p[b0]: sum_i v_i base^(i - g T)
-template <class FrP>
+template <class FrP, int REV = 0>
 __device__ __forceinline__ Fp<FrP> poly_lane_horner(const Fp<FrP> *v, size_t m, size_t g, unsigned tb, const Fp<FrP> &base) {
     const size_t lo = g << tb, hi = min(lo + ((size_t)1 << tb), m);
     Fp<FrP> acc = Fp<FrP>::zero();
     if (lo < hi) {
-        acc = fft_load(v, hi - 1);
+        acc = fft_load(v, poly_index<REV>(hi - 1, m));
 #pragma nounroll
-        for (size_t i = hi - 1; i > lo; --i) acc = fp_add(fp_mul(acc, base), fft_load(v, i - 1));
+        for (size_t i = hi - 1; i > lo; --i) acc = fp_add(fp_mul(acc, base), fft_load(v, poly_index<REV>(i - 1, m)));
     }
     return acc;
 }
 
 // The walk of lane g from its top coefficient down with carry-in y (the suffix value just above the lane): y_i = v_i + base y,
 // y_i stored at out[i - shift] (shift 1: the quotient h; 0: the suffix values themselves); y_0 -> *value
-template <class FrP>
+template <class FrP, int REV = 0>
 __device__ __forceinline__ void poly_lane_walk(const Fp<FrP> *v, size_t m, size_t g, unsigned tb, const Fp<FrP> &base, Fp<FrP> y,
                                                Fp<FrP> *out, unsigned shift, Fp<FrP> *value) {
     const size_t lo = g << tb, hi = min(lo + ((size_t)1 << tb), m);
 #pragma nounroll
     for (size_t i = hi; i > lo; --i) {
-        y = fp_add(fp_mul(y, base), fft_load(v, i - 1));
+        y = fp_add(fp_mul(y, base), fft_load(v, poly_index<REV>(i - 1, m)));
         if (out != nullptr && i - 1 >= shift) fft_store(out, i - 1 - shift, y);
     }
     if (lo == 0 && lo < hi && value != nullptr) fft_store(value, 0, y);
 }
 
 // Passes 1 and 2. One workgroup = one tile of TPB lanes x T coefficients. FUSED = 0: writes X_l (x_out, one per lane) and
-// S_t (s_out, one per tile). FUSED = 1 (one tile, gridDim.x == 1): the walk follows the scan in the same launch.
-template <class FrP, int FUSED>
+// S_t (s_out, one per tile). FUSED = 1 (one tile, gridDim.x == 1): the walk follows the scan in the same launch. REV = 1 reads
+// v in bit-reversed order (evaluation only: out is null).
+template <class FrP, int FUSED, int REV = 0>
 __global__ void __launch_bounds__(POLY_TPB) k_poly_lanes(const Fp<FrP> *__restrict__ v, size_t m, FftPowers<FrP> pw, unsigned b0,
                                                          unsigned tb, Fp<FrP> *__restrict__ x_out, Fp<FrP> *__restrict__ s_out,
                                                          Fp<FrP> *__restrict__ out, unsigned shift, Fp<FrP> *__restrict__ value) {
@@ -68,7 +77,7 @@ __global__ void __launch_bounds__(POLY_TPB) k_poly_lanes(const Fp<FrP> *__restri
     __shared__ Fr lane[POLY_TPB];
     const unsigned l = threadIdx.x;
     const size_t g = (size_t)blockIdx.x * POLY_TPB + l;
-    Fr x = poly_lane_horner(v, m, g, tb, pw.p[b0]);
+    Fr x = poly_lane_horner<FrP, REV>(v, m, g, tb, pw.p[b0]);
     lane[l] = x;
     // suffix scan: after step j, x_l = sum over lanes l..l + 2^(j+1) - 1 of s_m a^(T (m - l))
 #pragma nounroll
@@ -88,7 +97,7 @@ __global__ void __launch_bounds__(POLY_TPB) k_poly_lanes(const Fp<FrP> *__restri
     } else {
         __syncthreads();
         const Fr cin = l + 1 < POLY_TPB ? lane[l + 1] : Fr::zero();
-        poly_lane_walk(v, m, g, tb, pw.p[b0], cin, out, shift, value);
+        poly_lane_walk<FrP, REV>(v, m, g, tb, pw.p[b0], cin, out, shift, value);
     }
 }
 

@@ -15,6 +15,18 @@ here through fft.Domain, on copies: inputs are never modified. Errors raise Valu
 (ErrNumberPolynomials, ErrInconsistentSize, ErrSizeNotPowerOfTwo, ErrInconsistentSizeDomain) or the library's.
 The *_device variants take raw device pointers (e.g. torch tensor.data_ptr()) of Lagrange-basis vectors and the stream
 that produced them.
+
+The rest of the package (polynomial.go, quotient.go) over gmsm_iop_to_basis, gmsm_iop_evaluate and
+gmsm_iop_divide_by_x_minus_one:
+
+    p = NewPolynomial("bn254", coeffs, Form(Canonical, Regular))      # polynomial.go:73-78, coeffs shared, not copied
+    p.ToLagrange(d); p.ToCanonical(d); p.ToLagrangeCoset(d)           # :287-390, grow included; in place, return p
+    p.ToRegular(); p.ToBitReverse(); p.Shift(1); p.GetCoeff(i); p.Clone(); p.ShallowClone(); p.Size(); p.SetSize(n)
+    y = p.Evaluate(x)                                                 # :104-132; 0 for x in the domain of a Lagrange basis
+    q = DivideByXMinusOne(h, (small, big))                            # quotient.go:21-53: Canonical / Regular
+
+with to_basis_device, evaluate_device and divide_by_x_minus_one_device over raw device pointers. iop.Evaluate(f Expression,
+...) takes an arbitrary function and stays on the host.
 """
 import ctypes
 from collections import namedtuple
@@ -206,3 +218,149 @@ def build_ratio_shuffled_vectors_device(domain, d_num, num_layouts, d_den, den_l
     _check(_lib.load().gmsm_iop_ratio_shuffled(domain.handle, None, d_num, None, d_den, len(ln), ln.ctypes.data_as(_u32p),
                                                ld.ctypes.data_as(_u32p), _ptr(beta), int(expectedForm[0]), int(expectedForm[1]),
                                                stream or None, None, d_out))
+
+
+# ---- iop.Polynomial (polynomial.go) and iop.DivideByXMinusOne (quotient.go) over gmsm_iop_to_basis, gmsm_iop_evaluate and
+# gmsm_iop_divide_by_x_minus_one
+ErrMustBeLagrangeCoset = "the basis must be LagrangeCoset"
+
+
+def to_basis_device(domain, d_a, length, form, to_basis, stream=0):
+    """ToLagrange / ToCanonical / ToLagrangeCoset in place on the domain.Cardinality elements at device pointer d_a, of which
+    the first `length` are given (the rest is zeroed: the reference's grow); returns the layout the reference leaves."""
+    out_layout = ctypes.c_int(0)
+    _check(_lib.load().gmsm_iop_to_basis(domain.handle, None, d_a, int(length), int(form[0]), int(form[1]), int(to_basis), stream or None,
+                                         ctypes.byref(out_layout)))
+    return out_layout.value
+
+
+def evaluate_device(curve, d_polys, k, length, size, basis, layouts, shift, coset, x, stream=0):
+    """Evaluate of k polynomials of `length` coefficients concatenated at device pointer d_polys: (k, fr_limbs) values."""
+    c = _curve(curve)
+    lay = _layouts(layouts)
+    out = np.zeros((int(k), c.fr_limbs), dtype=np.uint64)
+    cs = None if coset is None else _elem(c, coset)
+    _check(_lib.load().gmsm_iop_evaluate(_gid(c), None, d_polys, int(k), int(length), int(size), int(basis), lay.ctypes.data_as(_u32p), int(shift),
+                                         None if cs is None else _ptr(cs), _ptr(_elem(c, x)), stream or None, _ptr(out)))
+    return out
+
+
+def divide_by_x_minus_one_device(domains, d_a, form, shift, d_out, stream=0):
+    """DivideByXMinusOne of the domains[1].Cardinality elements at device pointer d_a (a polynomial of size
+    domains[0].Cardinality, shifted by `shift`) into d_out: Canonical basis, Regular layout."""
+    _check(_lib.load().gmsm_iop_divide_by_x_minus_one(domains[0].handle, domains[1].handle, None, d_a, int(form[0]), int(form[1]), int(shift),
+                                                      stream or None, None, d_out))
+
+
+class Polynomial:
+    """iop.Polynomial (polynomial.go:62-78): coefficients (a numpy (n, fr_limbs) array, shared, not copied), Basis, Layout, shift,
+    size and coset. It iterates as (coeffs, basis, layout), so the BuildRatio* functions above take it as it is."""
+
+    def __init__(self, curve, coeffs, form):
+        self.curve = _curve(curve)
+        a = np.ascontiguousarray(coeffs, dtype=np.uint64)  # the array itself when it is already contiguous uint64: shared
+        self.coefficients = a if a.ndim == 2 and a.shape[1] == self.curve.fr_limbs else a.reshape(-1, self.curve.fr_limbs)
+        self.Basis, self.Layout = int(form[0]), int(form[1])
+        self.shift, self.size = 0, self.coefficients.shape[0]
+        self.coset = np.zeros(self.curve.fr_limbs, dtype=np.uint64)
+
+    def __iter__(self):
+        return iter((self.coefficients, self.Basis, self.Layout))
+
+    @property
+    def Form(self):
+        return Form(self.Basis, self.Layout)
+
+    def Shift(self, shift):
+        self.shift = int(shift)
+        return self
+
+    def Size(self):
+        return self.size
+
+    def SetSize(self, size):
+        self.size = int(size)
+
+    def ShallowClone(self):
+        res = Polynomial(self.curve, self.coefficients, (self.Basis, self.Layout))
+        res.coefficients = self.coefficients  # the same vector
+        res.shift, res.size, res.coset = self.shift, self.size, self.coset.copy()
+        return res
+
+    def Clone(self):
+        res = self.ShallowClone()
+        res.coefficients = self.coefficients.copy()
+        return res
+
+    def Coefficients(self):
+        return self.coefficients
+
+    def GetCoeff(self, i):
+        """polynomial.go:151-163: the i-th entry, taking shift and layout in account"""
+        n = self.coefficients.shape[0]
+        j = (i + (n // self.size) * self.shift) % n
+        if self.Layout != Regular:
+            bits = n.bit_length() - 1
+            j = int(format(j, "0%db" % bits)[::-1], 2) if bits else 0
+        return self.coefficients[j]
+
+    def _to_layout(self, layout):
+        if self.Layout != layout:
+            self.coefficients[:] = fft.BitReverse(self.curve, self.coefficients)
+            self.Layout = layout
+        return self
+
+    def ToRegular(self):
+        return self._to_layout(Regular)
+
+    def ToBitReverse(self):
+        return self._to_layout(BitReverse)
+
+    def _to_basis(self, d, basis):
+        n, card = self.coefficients.shape[0], d.Cardinality
+        buf = self.coefficients
+        if n < card:  # grow: the entry zeroes the tail
+            buf = np.empty((card, self.curve.fr_limbs), dtype=np.uint64)
+            buf[:n] = self.coefficients
+        out_layout = ctypes.c_int(0)
+        _check(_lib.load().gmsm_iop_to_basis(d.handle, _ptr(buf), None, n, self.Basis, self.Layout, basis, None, ctypes.byref(out_layout)))
+        self.coefficients, self.Basis, self.Layout = buf, basis, out_layout.value
+        return self
+
+    def ToLagrange(self, d):
+        return self._to_basis(d, Lagrange)
+
+    def ToCanonical(self, d):
+        return self._to_basis(d, Canonical)
+
+    def ToLagrangeCoset(self, d):
+        self.coset = np.array(d.FrMultiplicativeGen, dtype=np.uint64)  # cosetTable[1], whatever the form (polynomial.go:364)
+        return self._to_basis(d, LagrangeCoset)
+
+    def Evaluate(self, x):
+        """(*Polynomial).Evaluate (polynomial.go:104-132): one fr.Element. A shift outside 0..5 raises ValueError."""
+        if self.shift < 0:
+            raise ValueError("gmsm_iop_evaluate: shift %d is outside 0..5 (the reference evaluates at 0 there)" % self.shift)
+        lay = _layouts([self.Layout])
+        out = np.zeros(self.curve.fr_limbs, dtype=np.uint64)
+        _check(_lib.load().gmsm_iop_evaluate(_gid(self.curve), _ptr(self.coefficients), None, 1, self.coefficients.shape[0], self.size, self.Basis,
+                                             lay.ctypes.data_as(_u32p), self.shift, _ptr(self.coset), _ptr(_elem(self.curve, x)), None, _ptr(out)))
+        return out
+
+
+def NewPolynomial(curve, coeffs, form):
+    """iop.NewPolynomial (polynomial.go:73-78): the coefficients are not copied."""
+    return Polynomial(curve, coeffs, form)
+
+
+def DivideByXMinusOne(a, domains):
+    """iop.DivideByXMinusOne (quotient.go:21-53): a (LagrangeCoset, len = domains[1].Cardinality, size = domains[0].Cardinality)
+    divided by X^size - 1: a new Polynomial, Canonical / Regular, size = a.size. a is not modified."""
+    if a.Basis != LagrangeCoset:
+        raise ValueError(ErrMustBeLagrangeCoset)
+    out = np.zeros_like(a.coefficients)
+    _check(_lib.load().gmsm_iop_divide_by_x_minus_one(domains[0].handle, domains[1].handle, _ptr(a.coefficients), None, a.Basis, a.Layout,
+                                                      a.shift % (1 << 64), None, _ptr(out), None))
+    res = Polynomial(a.curve, out, (Canonical, Regular))
+    res.size = a.size
+    return res

@@ -460,6 +460,49 @@ int gmsm_iop_ratio_shuffled(uint64_t domain, const uint64_t *num, const void *d_
                             const void *d_den, size_t m, const uint32_t *num_layouts, const uint32_t *den_layouts,
                             const uint64_t *beta, int basis, int layout, void *hip_stream, uint64_t *out, void *d_out);
 
+/* ---- iop.Polynomial (ecc/<curve>/fr/iop/polynomial.go) and iop.DivideByXMinusOne (quotient.go:21-79) on the device
+ *      (gmsm_iop_poly.h): the rest of package iop, so that a polynomial the ratio entries read from HBM goes on to the
+ *      coset of the big domain, through the quotient and to its evaluations without coming back to the host. Conventions,
+ *      basis values (1 / 2 / 4) and layout values (8 / 16) are those of the ratio entries above; results are the reference's
+ *      bit for bit.
+ *   gmsm_iop_to_basis: (*Polynomial).ToLagrange / ToCanonical / ToLagrangeCoset (polynomial.go:287-390), IN PLACE (the one
+ *      entry that modifies its argument). The buffer holds cardinality elements of which the first len are given; the call
+ *      zeroes [len, cardinality) first - the reference's grow, which appends physically whatever the layout - also when the
+ *      basis is already to_basis, then runs the transforms of the reference's switch (none, one, or two enqueued back to
+ *      back with no host wait in between) and stores the layout the reference leaves in *out_layout: unchanged where
+ *      nothing or two transforms run, flipped where one does. len == 0 gives cardinality zeros; len > cardinality is an
+ *      error (the reference would hand fft a vector longer than the domain).
+ *   gmsm_iop_evaluate: (*Polynomial).Evaluate (polynomial.go:104-132, 198-261) for k >= 1 polynomials of len coefficients
+ *      each, concatenated, which share basis, size, shift and coset; layouts[j] (host) per polynomial; out_values (host)
+ *      receives k elements. In the reference's order: basis LagrangeCoset: x <- x / coset with 0^-1 = 0 - a polynomial that
+ *      never went through ToLagrangeCoset has coset 0 and is evaluated at 0, here as in the reference (coset may be NULL for
+ *      the other bases); shift != 0: x <- x g^shift with g = fft.Generator(size), the generator of the next power of two
+ *      >= size, not of len; Canonical basis: Horner over index i (Regular) or bitrev(i) (BitReverse); Lagrange and
+ *      LagrangeCoset: barycentric, with w = fft.Generator(len),
+ *        value = ((x^len - 1) / len) sum_i w^i c[idx(i)] / (x - w^i), 1/0 = 0 in the batch inversion.
+ *      For x in the domain {w^i} the prefactor is zero and the result is 0: the reference's answer, NOT the interpolated
+ *      value c[idx(i)]. Departure from the reference: a shift outside 0..5 is refused (GMSM_ERR_ARG); the reference
+ *      multiplies x by an element it never initialised there and so evaluates at 0 - that defect is not reproduced.
+ *   gmsm_iop_divide_by_x_minus_one: `a` holds N = card(domain_big) elements of a polynomial of size n = card(domain_small)
+ *      in basis 4 (LagrangeCoset; any other basis: "the basis must be LagrangeCoset"), rho = N / n. For i in [0, N):
+ *        out[bitrev(i)] = a.GetCoeff(i) inv[i mod rho], GetCoeff(i) = element (i + rho shift) mod N of a read through its
+ *        layout (polynomial.go:151-163), inv[j] = 1 / (g^n t^j - 1), g = the big domain's FrMultiplicativeGen, t = its
+ *        Generator^n (kept on the big domain per n after the first call),
+ *      then FFTInverse(DIT, OnCoset) over the big domain: N elements in Canonical basis, Regular layout, to out / d_out.
+ *   Errors are GMSM_ERR_ARG with a text, before any device work where the host can decide: both or none of a pair; an
+ *      unknown basis or layout value (evaluate names the index: "layouts[j] = v is no layout"); an unknown domain handle
+ *      ("unknown fft domain handle"); to_basis: len > cardinality, out_layout null; evaluate: k == 0, len == 0, size == 0,
+ *      x / out_values null, coset null with basis 4, shift > 5, len no power of two in a Lagrange basis or with a
+ *      BitReverse layout, len (Lagrange bases) or size (shift != 0) beyond the field's 2-adicity; quotient: domains of
+ *      different curves, n > N, an output that overlaps the input wholly or in part. ---- */
+int gmsm_iop_to_basis(uint64_t domain, uint64_t *a, void *d_a, size_t len, int basis, int layout, int to_basis,
+                      void *hip_stream, int *out_layout);
+int gmsm_iop_evaluate(int group, const uint64_t *polys, const void *d_polys, size_t k, size_t len, size_t size,
+                      int basis, const uint32_t *layouts, unsigned shift, const uint64_t *coset, const uint64_t *x,
+                      void *hip_stream, uint64_t *out_values);
+int gmsm_iop_divide_by_x_minus_one(uint64_t domain_small, uint64_t domain_big, const uint64_t *a, const void *d_a,
+                                   int basis, int layout, uint64_t shift, void *hip_stream, uint64_t *out, void *d_out);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals
