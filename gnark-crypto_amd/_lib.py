@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "gmsm_fr_batch_invert", "gmsm_iop_ratio_copy_constraint", "gmsm_iop_ratio_shuffled",
     "gmsm_iop_to_basis", "gmsm_iop_evaluate", "gmsm_iop_divide_by_x_minus_one",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
-    "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_debug_fold_planes", "gmsm_debug_plane_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
+    "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_debug_run_layout", "gmsm_debug_fold_planes", "gmsm_debug_plane_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
     "gmsm_device_count", "gmsm_set_device", "gmsm_last_error",
     "gmsm_version",
@@ -97,6 +97,8 @@ def load():
     L.gmsm_debug_plane_runs.argtypes = []
     L.gmsm_debug_fold_planes.restype = ctypes.c_int
     L.gmsm_debug_fold_planes.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, u64p, u64p]
+    L.gmsm_debug_run_layout.restype = ctypes.c_int
+    L.gmsm_debug_run_layout.argtypes = [ctypes.c_int, ctypes.c_int, sz] + [ctypes.c_uint] * 3 + [ctypes.c_int] * 2 + [ctypes.c_uint, u64p]
     L.gmsm_debug_reduce_shape.restype = ctypes.c_int
     L.gmsm_debug_reduce_shape.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     L.gmsm_multiexp_bases.restype = ctypes.c_int

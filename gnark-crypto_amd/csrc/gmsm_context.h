@@ -56,8 +56,7 @@ struct DeviceBuffer {
 
 // Process-wide switches (gmsm_set_option / gmsm_get_option, include/gmsm.h). The two a deployment may want - the window
 // width and the window-table policy - take their initial value from the environment ONCE, when the library is loaded
-// (GMSM_C, GMSM_TABLES); nothing on a call path reads the environment. The other two exist for the tests of the
-// point-range splits.
+// (GMSM_C, GMSM_TABLES); nothing on a call path reads the environment. The others exist for the tests and the A/B tools.
 struct Options {
     std::atomic<unsigned> window_bits{0};  // GMSM_OPT_WINDOW_BITS: 0 = the measured table (preferred_c), 2..20 forced
     std::atomic<unsigned> tables{1};       // GMSM_OPT_TABLES: 0 never, 1 the measured call sizes, 2 every size
@@ -66,9 +65,9 @@ struct Options {
     std::atomic<unsigned> fixed_base_bits{0};  // GMSM_OPT_FIXED_BASE_BITS: table width of the fixed-base batch (0 = by size)
     std::atomic<unsigned> spin_wait_us{0};     // GMSM_OPT_SPIN_WAIT_US: poll a call's stream this long before blocking on it (0 = park at once)
     std::atomic<unsigned> small_bits{0};       // GMSM_OPT_SMALL_BITS: the fused small-n kernel: 0 = on, width by size; 1 = off; 2..7 = on, this width
-    std::atomic<unsigned> split{0};            // GMSM_OPT_SPLIT (experiment): two window groups, the first group's fix-up + reduction beside the second's accumulation
+    std::atomic<unsigned> retired_split{0};    // GMSM_OPT_SPLIT (retired experiment): stored and read back, nothing looks at it
     std::atomic<unsigned> small_max{0};        // GMSM_OPT_SMALL_MAX: largest call the fused kernel takes (0 = the measured default)
-    std::atomic<unsigned> glv{1};              // GMSM_OPT_GLV: half scalars (gmsm_glv.h): 0 never, 1 the fused small-n kernel, 2 the sorted pipeline too
+    std::atomic<unsigned> glv{1};              // GMSM_OPT_GLV: half scalars (gmsm_glv.h): 0 never, 1 the fused small-n kernel and the sorted pipeline where measured ahead (glv_preferred_c), 2 every unregistered call
     std::atomic<unsigned> small_quad{0};       // GMSM_OPT_SMALL_QUAD: bucket phase of the fused kernel on lane quads: 0 by size, 1 never (narrow types), 2 always
     std::atomic<unsigned> poly_lane_bits{0};   // GMSM_OPT_POLY_LANE_BITS (tests): 0 = lane width of the suffix scan by length, k in 1..6 = 2^(k-1) coefficients
     std::atomic<unsigned> reduce_shape{0};     // GMSM_OPT_REDUCE_SHAPE (tests): 0 = the reduction's cost model; packed log2L | levels << 4 | combine kernel << 6
@@ -740,6 +739,8 @@ struct GroupVTable {
     int (*debug_glv_split)(const uint64_t *scalars, size_t n, uint32_t *out);  // test hook of gmsm_glv.h
     void (*plan_info)(size_t n, unsigned *c, unsigned *nwin, unsigned *entries_per_point, unsigned *fused);  // gmsm_default_plan
     void (*reduce_shape)(const Context &ctx, uint32_t nw, uint32_t nbuckets, uint32_t out[6]);  // gmsm_debug_reduce_shape
+    int (*run_layout)(int num_cus, size_t n, unsigned c, unsigned win_first, unsigned win_stride, bool glv, bool shared, unsigned flags,
+                      uint64_t *out);  // gmsm_debug_run_layout
     void (*fold_planes)(const uint64_t *planes, unsigned c, unsigned nwin, unsigned log2L, unsigned nhigh, uint64_t *out_jac);  // gmsm_debug_fold_planes
     // KZG opening over the group's scalar field (gmsm_poly.h): polynomials are host (`polys`) or device (`d_polys`) fr.Element
     // vectors, k of them concatenated (lens[i] elements each), never modified

@@ -1862,6 +1862,14 @@ GMSM_EXPORT int gmsm_debug_reduce_shape(int group, uint32_t nw, uint32_t nbucket
     return GMSM_OK;
 }
 
+GMSM_EXPORT int gmsm_debug_run_layout(int group, int num_cus, size_t n, unsigned c, unsigned win_first, unsigned win_stride, int glv,
+                                      int shared, unsigned flags, uint64_t *out) {
+    VT_OR_FAIL(group);
+    if (num_cus < 1 || num_cus > 4096 || n == 0 || c < 1 || c > 24 || flags > 31 || (flags >> 3) > 2 || !out)
+        return fail(GMSM_ERR_ARG, "gmsm_debug_run_layout: 1 <= num_cus <= 4096, n >= 1, 1 <= c <= 24, flags as documented");
+    return vt->run_layout(num_cus, n, c, win_first, win_stride, glv != 0, shared != 0, flags, out);
+}
+
 GMSM_EXPORT int gmsm_debug_fold_planes(int group, unsigned c, unsigned nwin, unsigned log2L, unsigned nblocks1, const uint64_t *planes,
                                        uint64_t *out_jac) {
     VT_OR_FAIL(group);
@@ -2059,7 +2067,7 @@ static const OptionRow OPTION_ROWS[] = {
     {GMSM_OPT_SMALL_BITS, &Options::small_bits, [](unsigned v) { return v <= 7; },
      "GMSM_OPT_SMALL_BITS: 0 (on, width by size), 1 (off) or 2..7 (on, forced width)"},
     {GMSM_OPT_SMALL_MAX, &Options::small_max, nullptr, nullptr},
-    {GMSM_OPT_SPLIT, &Options::split, nullptr, nullptr, true},
+    {GMSM_OPT_SPLIT, &Options::retired_split, nullptr, nullptr, true},  // retired: accepted, no effect
     {GMSM_OPT_GLV, &Options::glv, [](unsigned v) { return v <= 2; }, "GMSM_OPT_GLV: 0 never, 1 where measured ahead, 2 every unregistered call"},
     {GMSM_OPT_SMALL_QUAD, &Options::small_quad, [](unsigned v) { return v <= 2; }, "GMSM_OPT_SMALL_QUAD: 0 by call size, 1 never, 2 always"},
     {GMSM_OPT_POLY_LANE_BITS, &Options::poly_lane_bits, [](unsigned v) { return v <= 6; },

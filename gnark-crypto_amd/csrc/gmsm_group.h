@@ -1,5 +1,6 @@
-// One (curve, group) instance of the engine: the pipeline driver (struct Group) over the host-side arithmetic of
-// gmsm_group_host.h. The test hooks live in gmsm_group_debug.h, the function table the C ABI dispatches through in
+// One (curve, group) instance of the engine: struct Group decides what a call runs as - the sorted-bucket pipeline of
+// gmsm_pipeline.h (its base class, over the host-side arithmetic of gmsm_group_host.h), the fused small-n kernel, window
+// tables, point ranges - and holds the group's other device entries. The test hooks live in gmsm_group_debug.h, the function table the C ABI dispatches through in
 // gmsm_group_vtable.h (both included at the end). Instantiated once per group in gmsm_group_inst.hip (one translation
 // unit per group so the six groups compile in parallel).
 #pragma once
@@ -10,10 +11,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "gmsm_context.h"
-#include "gmsm_group_host.h"
-#include "gmsm_kernels.h"
-#include "gmsm_fixup_q.h"
+#include "gmsm_pipeline.h"
 #include "gmsm_small.h"
 #include "gmsm_fixedbase.h"
 #include "gmsm_ingest.h"
@@ -29,47 +27,19 @@
 
 namespace gmsm {
 
-// Tuning constants of the pipeline geometry. In the shipped library GMSM_TUNE(NAME, default) IS its default, folded at
-// compile time - none of these is a run-time knob. An experiments build (-DGMSM_EXPERIMENTS, tools/build_ab.sh) reads
-// GMSM_<NAME> from the environment instead, which is how the defaults below were swept:
-//   LOG2L, REDUCE_LEVELS   buckets per serial reduction thread / two or three reduction levels (0 = the cost model)
-//   SEG, SEGMAX            entries per accumulation thread (0 = chosen per launch) and its cap
-//   PART_LOG2, STAGE_CAP   coarse partition population, staging slots of the fine sort
-//   DEVICE_RANGES          point ranges of a device-resident call beyond the pipeline-run cap
-#define GMSM_TUNE(NAME, DFLT) tune_uint("GMSM_" #NAME, (DFLT))
-
 // ------------------------------------------------------------------ one (curve, group)
-template <class T> struct LazyOf;
-template <class P> struct LazyOf<Fp<P>> { using type = FpU<P>; };
-template <class P> struct LazyOf<Fp2<P>> { using type = Fp2U<P>; };
-
 template <class F_, class FrP_, class Consts_, bool NEEDS_TORSION_>
-struct Group : GroupHost<F_, FrP_> {
-    using Host = GroupHost<F_, FrP_>;  // fold, fold_sets, generate_points, build_fixed_base_table, fold_powers
-    using Host::batch_to_affine;
-    using Host::build_fixed_base_table;
-    using Host::fold;
-    using Host::fold_planes;
-    using Host::fold_powers;
-    using Host::fold_sets;
-    using Host::generate_points;
-    using Host::scalar_mul;
-    using F = F_;
-    using FrP = FrP_;
-    using Consts = Consts_;                                   // curve coefficient, wire-format flag bits (gmsm_params32.h)
-    static constexpr bool NEEDS_TORSION = NEEDS_TORSION_;     // cofactor != 1: subgroup check beyond the curve equation
-    using Aff = Affine<F>;
-    using Ext = XYZZ<F>;
-    using J = Jac<F>;
-    static constexpr unsigned FR_BITS = FrP::BITS;
-    static constexpr size_t AFF_BYTES = sizeof(Aff);
+struct Group : Pipeline<F_, FrP_, Consts_> {
+    using Pipe = Pipeline<F_, FrP_, Consts_>;  // the sorted-bucket pipeline: plans, layout, stages, collection
+    using Host = GroupHost<F_, FrP_>;          // fold, fold_sets, generate_points, build_fixed_base_table, fold_powers
+    using Host::batch_to_affine, Host::build_fixed_base_table, Host::fold, Host::fold_planes, Host::fold_powers, Host::fold_sets;
+    using Host::generate_points, Host::scalar_mul;
+    using typename Pipe::Aff, typename Pipe::Consts, typename Pipe::Ext, typename Pipe::F, typename Pipe::FrP, typename Pipe::J;
+    using typename Pipe::OpsSerial, typename Pipe::U;
+    using Pipe::AFF_BYTES, Pipe::FR_BITS, Pipe::bucket_sets, Pipe::collect_folded, Pipe::collect_window_sums, Pipe::enqueue_reduce;
+    using Pipe::enqueue_window_sums, Pipe::glv_width_built, Pipe::make_plan, Pipe::make_plan_glv;
+    static constexpr bool NEEDS_TORSION = NEEDS_TORSION_;  // cofactor != 1: subgroup check beyond the curve equation
     static constexpr size_t SCALAR_BYTES = sizeof(Fp<FrP>);
-    // unsaturated-limb accumulation (gmsm_fieldu.h) for groups whose coordinates live in Fp; Fp2 groups use the generic
-    // saturated kernel
-    using U = typename LazyOf<F>::type;  // lazy element type: FpU<P> for Fp coordinates, Fp2U<P> for Fp2 coordinates
-    // Group operations are inlined where a kernel has ONE call site of the addition (k_accumulate_seg, k_fixup_seg,
-    // k_reduce_serial: a single inlined Fp2 or BW6-761 addition is 60-350 KB of code); everything that combines few
-    // elements (long chains, the reduction's combine and level 2) runs on lane quads with the operands in LDS (gmsm_quad.h).
     // fixed-base / normalisation / table-doubling kernels: every type inlines its group operations since the end of round 6 (the wide
     // types called theirs out of line through rounds 2-6 for code size: same-box A/B profiles/r06_fixed_base_inline_ab.log - BN254 G2
     // 2^20 17.7 -> 8.7 ms, BLS12-381 G2 34.4 -> 18.2, BW6-761 53.6 -> 36.1). -DGMSM_INLINE_OPS_BYTES=56 gives the old form back.
@@ -77,80 +47,7 @@ struct Group : GroupHost<F_, FrP_> {
 #define GMSM_INLINE_OPS_BYTES (28 * 4)
 #endif
     static constexpr bool INLINE_OPS = sizeof(U) <= GMSM_INLINE_OPS_BYTES;
-    using OpsSerial = UnsatOps<U>;
-    using OpsElem = typename OpsSerial::Elem;
-    // Level 1 of the bucket reduction = k_reduce_serial (one thread per L buckets, no LDS) + k_combine_q (COMBINE_N
-    // (S, W) pairs per workgroup of 4 * COMBINE_N threads); level 2 = k_reduce2_q, at most RED2_TPB level-1 results per window.
-#ifndef GMSM_FORK_CONVERT_LOG2
-#define GMSM_FORK_CONVERT_LOG2 18
-#endif
-    static constexpr size_t FORK_CONVERT_MIN = (size_t)1 << GMSM_FORK_CONVERT_LOG2;  // unregistered calls from here on rewrite their bases on a side stream
-    static constexpr int COMBINE_N = 64;
-    static constexpr int RED2_TPB = 64;
-    // The serial part itself runs on quads (k_reduce_serial_q) for every element type but the 9-limb prime field.
-    // Measured reduce times one-lane / quad serial (same box): BW6-761 2^20 1.85 / 1.13 ms, BLS12-381 G2 2^22 2.17 / 1.61,
-    // BN254 G2 2^20 0.955 / 0.906, BLS12-381 G1 2^22 0.675 / 0.601 (2^16: 0.688 / 0.611).
-#ifndef GMSM_SERIAL_QUAD_WORDS
-#define GMSM_SERIAL_QUAD_WORDS 14
-#endif
-    static constexpr bool SERIAL_QUAD = sizeof(U) >= GMSM_SERIAL_QUAD_WORDS * 4;
-#ifndef GMSM_SERIAL_Q_QUADS
-#define GMSM_SERIAL_Q_QUADS 64
-#endif
-    static constexpr int SERIAL_Q_QUADS = GMSM_SERIAL_Q_QUADS;  // quads per workgroup of k_reduce_serial_q (A/B: tools/build_ab.sh)
-    // The work-efficient combine (k_combine_we: half the issue work, one step more) where the combine is throughput-bound:
-    // the 9-limb field with at least two workgroups per CU. Measured k_combine_q / k_combine_we reduce times, BN254 G1:
-    // 2^16 0.293 / 0.277 ms, 2^18 0.337 / 0.308, 2^20 0.344 / 0.312, 2^24 0.465 / 0.433 - but 2^12 (a handful of
-    // workgroups: latency) 0.080 / 0.106, and the 14-limb field 0.628 / 0.68 (three workgroups per CU, not four).
-#ifndef GMSM_COMBINE_WE_WORDS
-#define GMSM_COMBINE_WE_WORDS 9
-#endif
-    static constexpr bool COMBINE_WE = sizeof(U) <= GMSM_COMBINE_WE_WORDS * 4;
-    // GMSM_OPT_REDUCE_SHAPE (tests) names the combine kernel in bits 6-7: 1 = k_combine_q, 2 = k_combine_we where it is compiled
-    static bool use_combine_we(const Context &ctx, uint32_t workgroups) {
-        const unsigned forced = (options().reduce_shape.load(std::memory_order_relaxed) >> 6) & 3u;
-        if (forced) return COMBINE_WE && forced == 2;
-        return COMBINE_WE && workgroups >= 2u * (uint32_t)ctx.num_cus;
-    }
-    // k_fixup_seg: followers a chain head adds itself (one-lane additions); longer chains go to k_fixup_long (quads, one
-    // workgroup per chain). Handing chains of 3+ links to the quads for the wide types was measured: no gain at 2^20
-    // (BW6-761 fixup 0.75 ms either way - it is 322 K two-link chains in five rounds of 512-register workgroups), and 2^16
-    // got slower (0.68 -> 2.6 ms: thousands of short chains, one workgroup each).
-    static constexpr uint32_t FIX_MAXWALK = FIXUP_MAXWALK;
-    // k_fixup_seg on lane quads (gmsm_fixup_q.h) for the element types whose one-lane addition spills: everything wider than
-    // the 14-limb prime field (BN254 G2, BLS12-381 G2, BW6-761). -DGMSM_FIXUP_QUAD_WORDS=1000 builds the one-lane form (A/B).
-#ifndef GMSM_FIXUP_QUAD_WORDS
-#define GMSM_FIXUP_QUAD_WORDS 15
-#endif
-    static constexpr bool FIXUP_QUAD = sizeof(U) >= GMSM_FIXUP_QUAD_WORDS * 4;
     static constexpr bool SKEWED_HOST_RANGES = AFF_BYTES <= 96;  // host_ranges / window_sums_from_host
-    // plan_geometry: combine workgroups resident on a CU (measured on the pieces of a window-sharded call and on single
-    // bucket sets, profiles/r03_reduce_levels.log: with one per CU the model kept few windows on the two-level form)
-    static constexpr size_t COMBINE_RESIDENT = sizeof(U) <= 36 ? 4 : sizeof(U) <= 56 ? 3 : sizeof(U) <= 72 ? 2 : 1;
-
-    static WindowPlan make_plan(unsigned c, unsigned win_first, unsigned win_stride) {
-        WindowPlan p;
-        p.c = c;
-        p.nwin_total = num_windows(FR_BITS, c);
-        unsigned lc = last_c(FR_BITS, c);
-        p.nbuckets = 1u << (std::max(c, lc) - 1);
-        p.win_first = win_first;
-        p.win_stride = win_stride ? win_stride : 1;
-        p.nwin_local = win_first < p.nwin_total ? (p.nwin_total - win_first + p.win_stride - 1) / p.win_stride : 0;
-        p.shared = 0;
-        p.glv = 0;
-        return p;
-    }
-    // the windows of the GLV half scalars (gmsm_glv.h): same rules over GLV_BITS bits
-    static constexpr unsigned GLV_BITS = (unsigned)FrP::GLV_BITS;
-    static WindowPlan make_plan_glv(unsigned c, unsigned win_first, unsigned win_stride) {
-        WindowPlan p = make_plan(c, win_first, win_stride);
-        p.nwin_total = num_windows(GLV_BITS, c);
-        p.nbuckets = 1u << (std::max(c, last_c(GLV_BITS, c)) - 1);
-        p.nwin_local = win_first < p.nwin_total ? (p.nwin_total - win_first + p.win_stride - 1) / p.win_stride : 0;
-        p.glv = 1;
-        return p;
-    }
 
     // Runs the device pipeline for the windows of `plan`; host_xyzz receives plan.nwin_local window totals.
     // d_points: Go-layout affine bases on the device, or nullptr when `resident` (bases already rewritten into the lazy
@@ -161,9 +58,10 @@ struct Group : GroupHost<F_, FrP_> {
                            const ResidentBases *resident = nullptr, size_t resident_offset = 0) {
         int rc = order_after(ws, caller_stream);
         if (rc) return rc;
-        if ((rc = enqueue_window_sums(ctx, ws, d_points, d_scalars, n, plan, ws.stream, resident, nullptr, resident_offset,
-                                      false, false, TAIL_IF_FORCED)))
-            return rc;
+        RunRequest rq;
+        rq.resident_offset = resident_offset;
+        rq.tail_mode = TAIL_IF_FORCED;
+        if ((rc = enqueue_window_sums(ctx, ws, d_points, d_scalars, n, plan, ws.stream, resident, rq))) return rc;
         return collect_window_sums(ws, ws.stream, plan.nwin_local, host_xyzz);
     }
     // The same for a caller that wants the folded MultiExp: the reduction may leave its scaling to the host fold.
@@ -171,715 +69,10 @@ struct Group : GroupHost<F_, FrP_> {
                                   const WindowPlan &plan, hipStream_t caller_stream, J *out, const ResidentBases *resident) {
         int rc = order_after(ws, caller_stream);
         if (rc) return rc;
-        if ((rc = enqueue_window_sums(ctx, ws, d_points, d_scalars, n, plan, ws.stream, resident, nullptr, 0, false, false, TAIL_AUTO)))
-            return rc;
+        RunRequest rq;
+        rq.tail_mode = TAIL_AUTO;
+        if ((rc = enqueue_window_sums(ctx, ws, d_points, d_scalars, n, plan, ws.stream, resident, rq))) return rc;
         return collect_folded(ws, ws.stream, plan.c, plan.nwin_total, out);
-    }
-
-    // GMSM_OPT_REDUCE_TAIL: what a caller of enqueue_window_sums can take from ws.pinned - window totals only, plane sums
-    // when the option forces them (it converts them to totals itself: collect_window_sums), plane sums whenever they pay
-    // (it folds on the host: collect_folded).
-    enum { TAIL_LADDER = 0, TAIL_IF_FORCED = 1, TAIL_AUTO = 2 };
-#ifndef GMSM_PLANES_AUTO_WORDS
-#define GMSM_PLANES_AUTO_WORDS 9
-#endif
-    // groups whose MultiExp entries take the host planes by default: BN254 G1 (the 9-limb field), measured in
-    // profiles/reduce_planes_ab.md; the plane kernels exist for the groups that have k_combine_we
-    static constexpr bool PLANES_AUTO = sizeof(U) <= GMSM_PLANES_AUTO_WORDS * 4;
-    // first-level blocks per window the plane form takes (tested up to here). BN254 G1 at 2^20 - GLV half scalars, c = 16,
-    // 2^16 buckets, L = 8 - has 128; more would be a three-level plan at small L, which the cost model leaves to few windows.
-    static constexpr uint32_t PLANE_BLOCKS = 128;
-
-    // Waits for the pipeline enqueued on `stream` and hands out the window totals (pinned buffer -> host_xyzz).
-    static int collect_window_sums(Workspace &ws, hipStream_t stream, uint32_t nw, Ext *host_xyzz) {
-        if (nw == 0) return GMSM_OK;
-        HIP_TRY(wait_stream(stream));
-        if (ws.pending_timed) StageTimer::collect(ws);
-        ws.pending_timed = false;
-        if (ws.plane_np) {  // plane sums: every window's own Horner walk
-            const Ext *planes = (const Ext *)ws.pinned;
-            for (uint32_t w = 0; w < nw; ++w) {
-                const J j = fold_planes(planes + (size_t)w * ws.plane_np, 0, 1, ws.plane_log2L, ws.plane_np - 7);
-                host_xyzz[w] = j.z.is_zero() ? Ext::infinity() : xyzz_from_jac(j);
-            }
-            return GMSM_OK;
-        }
-        memcpy(host_xyzz, ws.pinned, (size_t)nw * sizeof(Ext));
-        return GMSM_OK;
-    }
-    // ... and folds them: msmReduceChunk over nwin window totals, or over their plane sums
-    static int collect_folded(Workspace &ws, hipStream_t stream, unsigned c, uint32_t nwin, J *out) {
-        if (ws.plane_np) {
-            HIP_TRY(wait_stream(stream));
-            if (ws.pending_timed) StageTimer::collect(ws);
-            ws.pending_timed = false;
-            *out = fold_planes((const Ext *)ws.pinned, c, nwin, ws.plane_log2L, ws.plane_np - 7);
-            return GMSM_OK;
-        }
-        std::vector<Ext> totals(nwin);
-        int rc = collect_window_sums(ws, stream, nwin, totals.data());
-        if (rc) return rc;
-        *out = fold(totals.data(), c, nwin);
-        return GMSM_OK;
-    }
-
-    // floor(r / 2^shift) for the scalar-field modulus r (the largest value a top window can hold, before the carry)
-    static uint64_t fr_modulus_shifted(unsigned shift) {
-        uint64_t v = 0;
-        for (int b = 62; b >= 0; --b) {
-            const unsigned bit = shift + (unsigned)b;
-            if (bit < 32u * FrP::N && ((FrP::Q[bit >> 5] >> (bit & 31)) & 1u)) v |= (uint64_t)1 << b;
-        }
-        return v;
-    }
-    // largest digit code k_decompose can emit for this plan (multiexp.go:779-800): decides uint16 vs uint32 digit arrays
-    static uint64_t max_digit_code(const WindowPlan &plan) {
-        if (plan.glv) {  // half scalars below 2^GLV_BITS: the top window holds at most 2^(its bits) (value + carry), code = 2 digit
-            const uint64_t low = ((uint64_t)1 << plan.c) - 1;
-            const unsigned top_bits = GLV_BITS - (plan.nwin_total - 1) * plan.c;
-            return std::max(low, (uint64_t)2 << top_bits);
-        }
-        const uint64_t low = ((uint64_t)1 << plan.c) - 1;
-        const unsigned top_shift = (plan.nwin_total - 1) * plan.c;
-        const uint64_t top = top_shift >= 63 + 32u * FrP::N ? 0 : ((fr_modulus_shifted(top_shift) + 1) << 1);
-        return plan.nwin_total > 1 ? std::max(low, top) : top;
-    }
-
-    // Accumulation and reduction geometry of one pipeline run over nw windows of n points.
-    struct Geometry {
-        uint32_t seg, tpw;                     // accumulation: entries per thread, threads per window
-        uint32_t log2L, nblocks1, log2span;    // reduction: buckets per serial thread, level-1 workgroups per window
-        uint32_t nblocks2;                     // 0: serial - combine - level 2; else a second combine of nblocks2 workgroups
-    };
-
-    static Geometry plan_geometry(const Context &ctx, uint32_t nw, size_t n, uint32_t NB, bool shared_set = false) {
-        Geometry q;
-        // reduction: buckets per serial thread, L = 2^log2L; COMBINE_N of their (S, W) pairs per combine workgroup; the
-        // last level (k_reduce2_q) takes at most RED2_TPB blocks per window, one quad each. Few windows of many buckets
-        // (one rank's share of a window-sharded call, the single bucket set of the window tables) would need a long
-        // serial walk to get there: a second combine level in between keeps L short.
-        constexpr size_t SPAN1 = COMBINE_N;  // pairs one combine workgroup takes
-        const auto blocks1 = [&](uint32_t l2) { return ((size_t)NB + (SPAN1 << l2) - 1) / (SPAN1 << l2); };
-        const auto blocks2 = [&](uint32_t l2) { return (blocks1(l2) + SPAN1 - 1) / SPAN1; };
-        // GMSM_OPT_REDUCE_SHAPE (tests; 0 = off): log2L in bits 0-3, the number of levels in bits 4-5
-        const unsigned forced_shape = options().reduce_shape.load(std::memory_order_relaxed);
-        uint32_t log2L = GMSM_TUNE(LOG2L, forced_shape & 15u);
-        const uint32_t force_levels = GMSM_TUNE(REDUCE_LEVELS, (forced_shape >> 4) & 3u);  // 2 / 3; 0 = cost model
-        bool three = force_levels == 3;
-        if (log2L == 0) {
-            // serial kernel: 2L dependent one-lane additions on every SIMD, as many rounds as the threads need;
-            // combine: 2 log2 N + log2 L + 1 quad steps (a quad step is about a third of a one-lane addition) per
-            // round of workgroups. Minimise the total in units of one-lane additions.
-            // The width of the TWO-level form is chosen with one combine workgroup per CU and round - the model all
-            // full-call configurations were measured with. Whether a second combine level pays is then decided with
-            // the workgroups a CU really holds at once (COMBINE_RESIDENT; their steps interleave): with one per CU the
-            // model kept few windows on a long serial walk (2^20 piece of 8: reduce 0.221 ms, 0.176 with three levels;
-            // 2^24 piece of 4: 0.358 / 0.271 - profiles/r03_reduce_levels.log).
-            const auto costs = [&](uint32_t l2, size_t resident, size_t *c3) {
-                const size_t serial_threads = (size_t)nw * (((size_t)NB + ((size_t)1 << l2) - 1) >> l2);
-                // lanes of the serial kernel: one per thread, or a quad per thread at a third of the step time
-                const size_t serial_lanes = SERIAL_QUAD ? 4 * serial_threads : serial_threads;
-                const size_t serial_rounds = (serial_lanes + (size_t)ctx.num_cus * 256 - 1) / ((size_t)ctx.num_cus * 256);
-                const size_t per_round = (size_t)ctx.num_cus * resident;
-                const size_t rounds = ((size_t)nw * blocks1(l2) + per_round - 1) / per_round;
-                const size_t cost_serial = (SERIAL_QUAD ? 1 : 3) * serial_rounds * ((size_t)2 << l2);
-                const size_t c2 = cost_serial + rounds * (2 * 6 + l2 + 1);
-                // second combine: its own rounds of 2 * 6 + 1 steps + the tail of the prescaling, and one more launch
-                const size_t rounds_b = ((size_t)nw * blocks2(l2) + per_round - 1) / per_round;
-                *c3 = c2 + rounds_b * (2 * 6 + 8) + 4;
-                return c2;
-            };
-            size_t best2 = ~(size_t)0, best3 = ~(size_t)0, unused = 0;
-            uint32_t l2_two = 0, l2_three = 0;
-            for (uint32_t l2 = 1; l2 <= 8; ++l2) {
-                const size_t c2 = costs(l2, 1, &unused);
-                if (blocks1(l2) <= (size_t)RED2_TPB && c2 < best2) {
-                    best2 = c2;
-                    l2_two = l2;
-                }
-                size_t c3 = 0;
-                (void)costs(l2, COMBINE_RESIDENT, &c3);
-                if (blocks1(l2) > 1 && blocks2(l2) <= (size_t)RED2_TPB && c3 < best3) {
-                    best3 = c3;
-                    l2_three = l2;
-                }
-            }
-            const size_t two_resident = l2_two ? costs(l2_two, COMBINE_RESIDENT, &unused) : ~(size_t)0;
-            if (force_levels == 3 ? l2_three != 0 : (force_levels != 2 && l2_three != 0 && best3 < two_resident)) {
-                log2L = l2_three;
-                three = true;
-            } else if (l2_two) {
-                log2L = l2_two;
-                three = false;
-            } else {
-                log2L = 8;
-            }
-        } else if (three && blocks1(log2L) <= 1) {
-            three = false;  // a forced width with three levels asked for: one combine workgroup leaves nothing for a second level
-        }
-        if (three) {
-            while (blocks2(log2L) > (size_t)RED2_TPB) ++log2L;
-        } else {
-            while (blocks1(log2L) > (size_t)RED2_TPB) ++log2L;
-        }
-        q.log2L = log2L;
-        q.nblocks1 = (uint32_t)blocks1(log2L);
-        q.nblocks2 = three ? (uint32_t)blocks2(log2L) : 0u;
-        q.log2span = log2L;
-        for (size_t t = SPAN1; t > 1; t >>= 1) ++q.log2span;
-        // entry-parallel segmented accumulation: seg entries per thread. Every thread does the same work, so the
-        // launch should be a whole number of resident "rounds" of WORKGROUPS: the grid is (blocks per window) x
-        // (windows), so the unit is a 256-thread block per window - nw * ceil(tpw/256) blocks must not exceed
-        // rounds x (CUs x resident blocks). (Counting threads instead put 24 x 11 = 264 blocks on 256 CUs for the
-        // 24 windows of BW6-761: eight blocks ran a second round alone and the kernel took twice as long - PMC:
-        // 1056 waves, each alive for half of the kernel.) Among the round counts that keep seg <= SEG_MAX the
-        // one that fills its last round best is taken.
-        uint32_t seg = GMSM_TUNE(SEG, 0);
-        if (seg == 0) {
-            const size_t cap_blocks = (size_t)ctx.num_cus * AccWaves<U>::value;
-            const size_t SEG_MAX = GMSM_TUNE(SEGMAX, 512);  // measured: 512 best at 2^24, 256 at 2^22
-            // Shortest segment. A launch that does not fill the chip is a latency chain of `seg` additions per thread:
-            // with sparse buckets (<= 8 entries each: few chains of partial sums to close) shorter segments on more
-            // threads win - BN254 G1 2^14 0.605 -> 0.476 ms, 2^16 0.637 -> 0.585, BLS12-381 G1 2^16 1.17 -> 0.98; crowded
-            // buckets (the 8-bit windows of small inputs) would pay it back in the fix-up (BLS12-381 G1 2^14: 0.13 -> 0.49 ms).
-            // Measured for the three narrow element types (profiles/r03_short_segments.log).
-            size_t seg_floor = 32;
-            if (sizeof(U) <= 72 && n / NB <= 8) {
-                const size_t entries = (size_t)nw * n, cap_threads = cap_blocks * 256;
-                seg_floor = entries / 8 <= cap_threads ? 8 : entries / 16 <= cap_threads ? 16 : 32;
-            } else if (sizeof(U) <= 72 && shared_set) {
-                // the shared bucket set of the window tables is crowded by construction, but its chains are closed one
-                // thread per bucket (k_fixup_bucket): BN254 G1 2^14 0.456 -> 0.365 ms at 8, 2^16 0.472 -> 0.400 at 16
-                // (0.428 at 8), 2^17 and up best at 32; BLS12-381 G1 2^15 0.775 -> 0.601 at 8, 2^16 0.817 -> 0.657 at 16;
-                // BN254 G2 (its one-lane additions cost three times as much) 2^15 1.088 -> 0.824 at 16, 2^16 best at 32
-                const size_t entries = (size_t)nw * n;
-                if (sizeof(U) <= 56) seg_floor = entries <= ((size_t)1 << 19) ? 8 : entries <= ((size_t)3 << 19) ? 16 : 32;
-                else seg_floor = entries <= ((size_t)3 << 18) ? 16 : 32;
-            }
-            size_t best_seg = 0, first_r = 0;
-            double best_fill = -1.0;
-            for (size_t r = 1; r < 100000; ++r) {
-                const size_t bpw = r * cap_blocks / nw;  // whole blocks per window in r rounds
-                if (bpw == 0) continue;
-                const size_t sg = std::max<size_t>((n + bpw * 256 - 1) / (bpw * 256), seg_floor);
-                if (sg > SEG_MAX) continue;
-                if (!first_r) first_r = r;
-                const size_t blocks = (size_t)nw * (((n + sg - 1) / sg + 255) / 256);
-                const double fill = (double)blocks / (double)(((blocks + cap_blocks - 1) / cap_blocks) * cap_blocks);
-                if (fill > best_fill + 1e-9) {
-                    best_fill = fill;
-                    best_seg = sg;
-                }
-                if (fill > 0.985 || r >= first_r + 5 || sg == seg_floor) break;
-            }
-            seg = (uint32_t)(best_seg ? best_seg : seg_floor);
-        }
-        q.seg = seg;
-        q.tpw = (uint32_t)((n + seg - 1) / seg);  // threads per window (upper bound: <= n entries)
-        return q;
-    }
-
-    // k_decompose for this plan: the unrolled kernel of the plan's width when it is one of the window table's
-    // (preferred_c), the generic one otherwise (forced and test widths). d16: uint16 digit codes.
-    static void launch_decompose(const void *d_scalars, size_t n, const WindowPlan &plan, bool d16, void *digits,
-                                 const uint8_t *skip, hipStream_t stream) {
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        if (plan.glv) {  // half scalars: digits[k][2 n] (glv_width_built() lists the widths)
-#define GMSM_DECOMPOSE_GLV(CC)                                                                                                  \
-    case CC:                                                                                                                    \
-        if (d16) hipLaunchKernelGGL((k_decompose_glv<FrP, uint16_t, CC>), grid, block, 0, stream, (const uint32_t *)d_scalars, n, \
-                                    plan, (uint16_t *)digits, skip);                                                             \
-        else hipLaunchKernelGGL((k_decompose_glv<FrP, uint32_t, CC>), grid, block, 0, stream, (const uint32_t *)d_scalars, n,     \
-                                plan, (uint32_t *)digits, skip);                                                                 \
-        return;
-            switch (plan.c) {
-                GMSM_DECOMPOSE_GLV(10) GMSM_DECOMPOSE_GLV(11) GMSM_DECOMPOSE_GLV(12) GMSM_DECOMPOSE_GLV(13) GMSM_DECOMPOSE_GLV(14)
-                GMSM_DECOMPOSE_GLV(15) GMSM_DECOMPOSE_GLV(16) GMSM_DECOMPOSE_GLV(17) GMSM_DECOMPOSE_GLV(18) GMSM_DECOMPOSE_GLV(20)
-                default: return;  // never planned (glv_width_built)
-            }
-#undef GMSM_DECOMPOSE_GLV
-        }
-#define GMSM_DECOMPOSE_C(CC)                                                                                                \
-    case CC:                                                                                                                \
-        if (d16) hipLaunchKernelGGL((k_decompose_c<FrP, uint16_t, CC>), grid, block, 0, stream, (const uint32_t *)d_scalars, n,  \
-                                    plan, (uint16_t *)digits, skip);                                                         \
-        else hipLaunchKernelGGL((k_decompose_c<FrP, uint32_t, CC>), grid, block, 0, stream, (const uint32_t *)d_scalars, n,      \
-                                plan, (uint32_t *)digits, skip);                                                             \
-        return;
-        switch (plan.c) {
-            GMSM_DECOMPOSE_C(8) GMSM_DECOMPOSE_C(9) GMSM_DECOMPOSE_C(10) GMSM_DECOMPOSE_C(12) GMSM_DECOMPOSE_C(13)
-            GMSM_DECOMPOSE_C(14) GMSM_DECOMPOSE_C(15) GMSM_DECOMPOSE_C(16) GMSM_DECOMPOSE_C(17) GMSM_DECOMPOSE_C(18)
-            GMSM_DECOMPOSE_C(20)
-            default: break;
-        }
-#undef GMSM_DECOMPOSE_C
-        if (d16)
-            hipLaunchKernelGGL((k_decompose<FrP, uint16_t>), grid, block, 0, stream, (const uint32_t *)d_scalars, n, plan,
-                               (uint16_t *)digits, skip);
-        else
-            hipLaunchKernelGGL((k_decompose<FrP, uint32_t>), grid, block, 0, stream, (const uint32_t *)d_scalars, n, plan,
-                               (uint32_t *)digits, skip);
-    }
-
-    // Launches every kernel of one pipeline run and queues the copy of the window totals into ws.pinned; does not wait.
-    // `stream` carries the call (inputs are ready there; the totals are complete there). All scratch comes from `ws`, so
-    // two workspaces can be in flight at once.
-    // d_out != nullptr: the totals stay on the device (copied to d_out in stream order) instead of going to ws.pinned.
-    // (Round 2 could cut the windows of a call into groups on two streams so that the reduction of one group ran under
-    // the accumulation of the next; measured slower in every configuration - profiles/r02_split_ab.log - and removed.)
-    // buckets_only: stop after the fix-up - ws.buckets / ws.starts hold the range's bucket sums (a range of a multi-range
-    // host call: k_merge_buckets adds them to the call's running buckets, ONE reduction at the end; enqueue_reduce).
-    static int enqueue_window_sums(Context &ctx, Workspace &ws, const void *d_points, const void *d_scalars, size_t n,
-                                   const WindowPlan &plan, hipStream_t stream, const ResidentBases *resident,
-                                   void *d_out = nullptr, size_t resident_offset = 0 /* first registered base used */,
-                                   bool buckets_only = false, bool time_range = false /* buckets_only: the caller collects the
-                                   stage events of this range before it enqueues the next (multiexp_device) */,
-                                   int tail_mode = TAIL_LADDER /* what the caller can take from ws.pinned */) {
-        const uint32_t nwd = plan.nwin_local;  // windows of the digit decomposition = totals handed out
-        ws.pending_timed = false;
-        ws.plane_np = 0;
-        if (nwd == 0) return GMSM_OK;
-        // window tables: the (window, point) pairs of all windows form ONE set of entries over one bucket set
-        const bool shared = plan.shared != 0;
-        if (shared && !(resident && resident->tab_c.load() == plan.c && plan.win_first == 0 && plan.win_stride == 1))
-            return fail(GMSM_ERR_ARG, "shared-bucket plan without matching window tables");
-        if (shared && n) g_table_runs.fetch_add(1, std::memory_order_relaxed);
-        if (ws.uncollected) {  // stage events of an enqueue-only call (nobody waited for it): pick them up now
-            if (ws.timed && hipEventQuery(ws.events[ws.timed_level == 2 ? T_FIXUP : T_END]) == hipSuccess) StageTimer::collect(ws);
-            ws.uncollected = false;
-        }
-        // The workspace may still be in use by work enqueued earlier on another stream: order behind it.
-        int rc;
-        if ((rc = begin_use(ws, stream))) return rc;
-        if (n == 0) {
-            int rc0 = ws.ensure_pinned((size_t)nwd * sizeof(Ext));
-            if (rc0) return rc0;
-            if (d_out) HIP_TRY(hipStreamSynchronize(stream));  // an earlier copy out of ws.pinned may be in flight
-            for (uint32_t k = 0; k < nwd; ++k) ((Ext *)ws.pinned)[k] = Ext::infinity();
-            if (d_out) {
-                HIP_TRY(hipMemcpyAsync(d_out, ws.pinned, (size_t)nwd * sizeof(Ext), hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-            }
-            return GMSM_OK;
-        }
-        const size_t n_points = n;  // scalars / bases of this run
-        const uint32_t nw = shared ? 1u : nwd;  // bucket sets: what the sort, the accumulation and the reduction see as windows
-        if (shared) n *= nwd;                   // ... and their entries
-        const bool glv = plan.glv != 0;         // half scalars: entry 2 i = (P_i, k1_i), entry 2 i + 1 = (phi(P_i), k2_i)
-        if (glv && (shared || resident)) return fail(GMSM_ERR_ARG, "GLV plan over registered bases");
-        if (glv) n *= 2;
-        if (n >= ((size_t)1 << 31)) return fail(GMSM_ERR_ARG, "n must be < 2^31");
-        const uint32_t NB = plan.nbuckets;
-        constexpr size_t REC = sizeof(typename OpsSerial::Mem);  // bucket / partial record (lazy representation on the fast path)
-
-        const Geometry q = plan_geometry(ctx, nw, n, NB, shared);
-        // GMSM_OPT_SPLIT (experiment): two window groups; each group's accumulation gets the segment length that fills the chip
-        // with HALF the windows (the reduction geometry stays the call's)
-        const bool split = options().split.load(std::memory_order_relaxed) != 0 && !buckets_only && !shared && nw >= 4 && q.nblocks2 == 0;
-        const Geometry qa = split ? plan_geometry(ctx, nw / 2, n, NB, shared) : q;  // accumulation + fix-up geometry
-        const size_t tot_thr = (size_t)nw * qa.tpw;
-        const size_t tot_blk = (size_t)nw * q.nblocks1;
-        // GMSM_OPT_REDUCE_TAIL: the reduction stops at its plane sums and the host fold scales them (k_plane_sums)
-        bool planes = false;
-        if constexpr (COMBINE_WE) {
-            const unsigned tail = options().reduce_tail.load(std::memory_order_relaxed);
-            const bool can = tail_mode != TAIL_LADDER && !d_out && !buckets_only && !shared && !split && q.nblocks1 <= PLANE_BLOCKS;
-            planes = can && (tail == 2 || (tail == 0 && tail_mode == TAIL_AUTO && PLANES_AUTO &&
-                                           options().reduce_shape.load(std::memory_order_relaxed) == 0));
-        }
-        uint32_t plane_h = 0;
-        while ((1u << plane_h) < q.nblocks1) ++plane_h;
-        const uint32_t plane_np = 7 + plane_h;
-
-        // ---- grouping geometry
-        uint32_t log2NB = 0;
-        while ((1u << log2NB) < NB) ++log2NB;
-        uint32_t log2n = 0;
-        while (((size_t)1 << log2n) < n) ++log2n;
-        const uint32_t lidx = log2n + 1;  // bits of (index << 1 | negate)
-        // target partition population 2^part_log2 (measured, BN254 G1: 2^13 is best up to 2^21 points - more
-        // workgroups for the fine pass; 2^15 from 2^24 on - 128-byte runs out of the coarse pass)
-        const uint32_t part_log2 = GMSM_TUNE(PART_LOG2, log2n <= 21 ? 13 : log2n >= 24 ? 15 : 14);
-        int fb = (int)part_log2 + (int)log2NB - (int)log2n;
-        if (fb > (int)log2NB) fb = (int)log2NB;
-        if (fb > 15) fb = 15;  // the fine pass keeps 2^fb counters in LDS (128 KiB): windows wider than 16 bits on few points
-        if (fb < 0) fb = 0;
-        if (fb + lidx > 32) fb = 32 - lidx;
-        const uint32_t fbits = (uint32_t)fb;
-        const uint32_t nparts = NB >> fbits;
-        const bool big_chunk = n > ((size_t)1 << 25) && (size_t)nparts * 8 + PART_CHUNK_BIG * 6 <= 152 * 1024;
-        const size_t pchunk_len = big_chunk ? PART_CHUNK_BIG : PART_CHUNK;  // chunk = one LDS staging buffer
-        const uint32_t pchunks = (uint32_t)((n + pchunk_len - 1) / pchunk_len);
-        const size_t scatter_lds = (size_t)nparts * 8 + pchunk_len * 6;
-        if (scatter_lds > 152 * 1024)  // 32-bit sort entries: bucket bits + index bits; reached beyond 2^27 points at c <= 17
-            return fail(GMSM_ERR_ARG, plan.c > 17 ? "window width too large for this many points in one pipeline run (a run takes up to "
-                                                    "2^(44-c) points for c > 17): use a smaller c or split by point range"
-                                                  : "more than 2^27 points in one pipeline run: split the window sums by point range "
-                                                    "and add the sets (gmsm_fold_window_sets); the MultiExp entries do this themselves");
-        // staging slots of the fine pass: up to 96 KiB next to the 2^fbits counters; larger partitions go direct
-        const size_t fine_cnt_bytes = (size_t)4 << fbits;
-        const uint32_t stage_cap = fine_cnt_bytes >= 156 * 1024 ? 0u
-                                   : (uint32_t)std::min<size_t>(GMSM_TUNE(STAGE_CAP, part_log2 >= 15 ? 39000 : 24576),
-                                                              (156 * 1024 - fine_cnt_bytes) / 4);
-        if (stage_cap > 40u * 1024u) return fail(GMSM_ERR_ARG, "window geometry: staging slots beyond the fine sort's registers");
-        if (fine_cnt_bytes + (size_t)stage_cap * 4 > 160 * 1024)  // cannot happen with fb <= 15; a failed launch must not
-            return fail(GMSM_ERR_ARG, "window geometry: fine-sort counters exceed the LDS");  // leave garbage for the next kernels
-        const bool d16 = max_digit_code(plan) < 65536;
-        const size_t dsz = d16 ? 2 : 4;
-
-        // ---- scratch
-        if ((rc = ws.digits.ensure((size_t)nw * n * dsz))) return rc;
-        if ((rc = ws.sorted.ensure((size_t)nw * n * 4))) return rc;
-        if ((rc = ws.parted.ensure((size_t)nw * n * 4))) return rc;
-        if ((rc = ws.starts.ensure((size_t)nw * (NB + 1) * 4))) return rc;
-        if ((rc = ws.buckets.ensure((size_t)nw * NB * REC))) return rc;
-        if ((rc = ws.partials.ensure(planes ? tot_blk * 8 * REC : (tot_blk + (size_t)nw * q.nblocks2) * 2 * REC))) return rc;
-        const uint32_t T = (uint32_t)(((size_t)NB + ((size_t)1 << q.log2L) - 1) >> q.log2L);  // (S, W) pairs per window of k_reduce_serial
-        if ((rc = ws.red_pre.ensure((size_t)nw * T * 2 * REC))) return rc;
-        if ((rc = ws.totals.ensure((size_t)nwd * sizeof(Ext)))) return rc;
-        if ((rc = ws.ensure_pinned((size_t)nwd * (planes ? plane_np : 1u) * sizeof(Ext)))) return rc;
-        if ((rc = ws.blockhist.ensure((size_t)nw * pchunks * nparts * 4))) return rc;
-        if ((rc = ws.counts.ensure((size_t)nw * (2 * nparts + 1) * 4))) return rc;
-        if ((rc = ws.seg_partials.ensure(tot_thr * 2 * REC))) return rc;
-        if ((rc = ws.seg_flags.ensure(tot_thr * 4))) return rc;
-        if ((rc = ws.seg_bucket.ensure(tot_thr * 4))) return rc;
-        // long-chain list of the fixup (the fix-up kernels append pieces of LONG_PIECE links, k_fixup_long consumes): one counter
-        // (slot of the first window; k_part_rowscan zeroes it) + the items: chains have more than FIX_MAXWALK followers
-        const size_t list_cap = 2 * (tot_thr / FIX_MAXWALK + tot_thr / LONG_PIECE + nw + 16);  // two halves: one per window group (GMSM_OPT_SPLIT)
-        if ((rc = ws.seg_lvl.ensure((size_t)nw * 4 + 16 + list_cap * sizeof(LongChain)))) return rc;
-        uint32_t *long_flag = (uint32_t *)ws.seg_lvl.ptr;                                  // [nw] counters, [0] is used
-        LongChain *long_list = (LongChain *)((char *)ws.seg_lvl.ptr + (((size_t)nw * 4 + 15) / 16) * 16);
-        const size_t piece_sums_off = ((list_cap * 4 + 15) / 16) * 16;
-        if ((rc = ws.long_pieces.ensure(piece_sums_off + list_cap * REC))) return rc;
-        uint32_t *piece_done = (uint32_t *)ws.long_pieces.ptr;
-        void *piece_sums = (char *)ws.long_pieces.ptr + piece_sums_off;
-        // oversized partitions of the fine sort (k_part_rowscan lists them, k_heavy_* sort them): a window has at most
-        // n / (stage_cap + 1) of them, and their sub-runs of HEAVY_SUB references number at most n / HEAVY_SUB + that
-        const uint32_t hcap = (uint32_t)std::min<size_t>(nparts, n / ((size_t)stage_cap + 1) + 1);
-        const uint32_t scap = (uint32_t)(n / HEAVY_SUB) + hcap;
-        const size_t hparts_bytes = (((size_t)nw * hcap * sizeof(HeavyPart) + 15) / 16) * 16, hcount_bytes = (((size_t)nw * 8 + 4 + 15) / 16) * 16;
-        if ((rc = ws.heavy.ensure(hparts_bytes + hcount_bytes + ((size_t)nw * scap << fbits) * 4))) return rc;
-        HeavyPart *hparts = (HeavyPart *)ws.heavy.ptr;
-        uint32_t *hcount = (uint32_t *)((char *)ws.heavy.ptr + hparts_bytes);
-        uint32_t *subhist = (uint32_t *)((char *)ws.heavy.ptr + hparts_bytes + hcount_bytes);
-        if (nw > HEAVY_MAX_WINDOWS) return fail(GMSM_ERR_ARG, "more than 256 windows in one pipeline run");
-        // workgroups of the heavy kernels (the sub-runs of all windows are taken round-robin): the chip twice over
-        const uint32_t heavy_wg = (uint32_t)std::min<size_t>((size_t)2 * ctx.num_cus, std::max<size_t>((size_t)nw * scap, 1));
-        uint32_t *bh = (uint32_t *)ws.blockhist.ptr, *part_base = (uint32_t *)ws.counts.ptr;
-        uint32_t *part_pop = part_base + (size_t)nw * (nparts + 1);
-
-        if ((rc = ctx.allow_lds((const void *)k_part_hist<uint16_t>, 160 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_part_hist<uint32_t>, 160 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_part_scatter<uint16_t, PART_CHUNK>, 152 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_part_scatter<uint32_t, PART_CHUNK>, 152 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_part_scatter<uint16_t, PART_CHUNK_BIG>, 152 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_part_scatter<uint32_t, PART_CHUNK_BIG>, 152 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_fine_sort<24>, 160 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_fine_sort<40>, 160 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_heavy_hist, 128 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_heavy_scan, 128 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_heavy_place, 128 * 1024))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_fixup_long<U>, (int)(128 * sizeof(QRec<U>))))) return rc;
-        if constexpr (FIXUP_QUAD)
-            if ((rc = ctx.allow_lds((const void *)k_fixup_seg_q<U>, (int)(128 * sizeof(QRec<U>))))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_combine_q<U, true, COMBINE_N>, (int)((2 * COMBINE_N + 1) * sizeof(QRec<U>))))) return rc;
-        if constexpr (COMBINE_WE)
-            if ((rc = ctx.allow_lds((const void *)k_combine_we<U, true>, (int)((2 * COMBINE_N + 1) * sizeof(QRec<U>))))) return rc;
-        if constexpr (SERIAL_QUAD)
-            if ((rc = ctx.allow_lds((const void *)k_reduce_serial_q<U, SERIAL_Q_QUADS>, (int)(3 * SERIAL_Q_QUADS * sizeof(QRec<U>))))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_reduce2_q<U, true>, (int)(2 * RED2_TPB * sizeof(QRec<U>))))) return rc;
-        if constexpr (COMBINE_WE) {
-            if (planes) {
-                if ((rc = ctx.allow_lds((const void *)k_combine_we<U, true, true>, (int)((2 * COMBINE_N + 1) * sizeof(QRec<U>))))) return rc;
-                if ((rc = ctx.allow_lds((const void *)k_plane_sums<U, true>, (int)(PLANE_BLOCKS * sizeof(QRec<U>))))) return rc;
-            }
-        }
-
-        // Stage times cover single-run calls: the ranges of a multi-range call (buckets_only) reuse a workspace's events
-        // before anybody could read them, and their merges and the one reduction run on another stream - such calls are
-        // left out of the profile instead of being reported with two of their ranges and no reduction.
-        StageTimer timer(ws, /*enabled=*/!buckets_only || time_range);
-        ws.timed = timer.on;
-        // ---- 0. inputs: rewrite the bases into the lazy Montgomery domain + infinity flags (unless registered earlier),
-        // signed-digit decomposition of every scalar
-        timer.mark(T_DECOMPOSE, stream);
-        const uint8_t *skip = nullptr;
-        const void *upoints = nullptr;
-        bool forked = false;
-        if (resident) {
-            upoints = (const char *)(shared ? resident->tables.ptr : resident->upoints.ptr) + resident_offset * AFF_BYTES;
-            skip = (const uint8_t *)resident->skip.ptr + resident_offset;
-        } else {
-            // Round 4: the rewrite of the bases runs on a stream of its own BESIDE the scalar pipeline (decomposition and
-            // the two sort passes touch only the scalars; those kernels are bound by LDS atomics and latency, the rewrite
-            // by HBM) and joins before the accumulation. Infinity points are recognised by the accumulation from the
-            // rewritten record (uaffine_is_infinity), so the decomposition needs no flags from here. 2^20: 36 us off the
-            // critical path, 2^24: 0.44 ms. Small calls keep the single stream (two events cost more than they hide).
-            if ((rc = ws.upoints.ensure((glv ? 2 : 1) * n_points * AFF_BYTES))) return rc;
-            forked = n_points >= FORK_CONVERT_MIN;
-            if (forked && (rc = ws.side_stream(ws.cstream))) return rc;
-            hipStream_t cs = forked ? ws.cstream : stream;
-            if (forked) {
-                HIP_TRY(hipEventRecord(ws.ev_fork, stream));
-                HIP_TRY(hipStreamWaitEvent(cs, ws.ev_fork, 0));
-            }
-            if (glv)
-                hipLaunchKernelGGL((k_convert_points_glv<U, Consts>), dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0,
-                                   cs, d_points, n_points, ws.upoints.ptr);
-            else
-                hipLaunchKernelGGL((k_convert_points<U>), dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0,
-                                   cs, d_points, n_points, ws.upoints.ptr, (uint8_t *)nullptr);
-            if (forked) {
-                ws.conv_pending = true;  // until the join below is enqueued (an error return in between leaves cstream running)
-                HIP_TRY(hipEventRecord(ws.ev_conv, cs));
-            }
-            upoints = ws.upoints.ptr;
-            skip = nullptr;
-        }
-        // (A decomposition fused with the coarse histogram was measured and dropped: one workgroup per 16 K-scalar chunk
-        // leaves 3/4 of the CUs idle at 2^20, and at 2^24 it only breaks even.)
-        // (shared: digits[w][i] of the n_points scalars, read from here on as one window of nwd * n_points entries)
-        launch_decompose(d_scalars, n_points, plan, d16, ws.digits.ptr, skip, stream);
-
-        const void *digits = ws.digits.ptr;
-        uint32_t *sorted = (uint32_t *)ws.sorted.ptr, *parted = (uint32_t *)ws.parted.ptr, *starts = (uint32_t *)ws.starts.ptr;
-        char *buckets = (char *)ws.buckets.ptr, *seg_partials = (char *)ws.seg_partials.ptr;
-        uint32_t *seg_flags = (uint32_t *)ws.seg_flags.ptr, *seg_bucket = (uint32_t *)ws.seg_bucket.ptr;
-
-        // ---- 1. group the point references of every window by bucket
-        timer.mark(T_HIST, stream);
-        if (d16)
-            hipLaunchKernelGGL(k_part_hist<uint16_t>, dim3(pchunks, nw), dim3(1024), (size_t)nparts * 4, stream,
-                               (const uint16_t *)digits, n, nparts, fbits, pchunk_len, bh);
-        else
-            hipLaunchKernelGGL(k_part_hist<uint32_t>, dim3(pchunks, nw), dim3(1024), (size_t)nparts * 4, stream,
-                               (const uint32_t *)digits, n, nparts, fbits, pchunk_len, bh);
-        timer.mark(T_SCAN, stream);
-        if ((size_t)((nparts + 31) / 32) * nw < (size_t)ctx.num_cus && pchunks >= 256)
-            hipLaunchKernelGGL(k_part_colscan<32>, dim3((nparts + 31) / 32, nw), dim3(1024), 0, stream, bh, pchunks, nparts, part_pop, hcount + 2 * nw);
-        else
-            hipLaunchKernelGGL(k_part_colscan<8>, dim3((nparts + 31) / 32, nw), dim3(256), 0, stream, bh, pchunks, nparts, part_pop, hcount + 2 * nw);
-        hipLaunchKernelGGL(k_part_rowscan, dim3(nw), dim3(1024), 0, stream, part_pop, nparts, part_base, long_flag, stage_cap, hparts,
-                           hcount, hcap);
-        timer.mark(T_SCATTER, stream);
-        {
-            const dim3 grid(pchunks, nw), block(1024);
-#define GMSM_SCATTER(D, CH)                                                                                              \
-    hipLaunchKernelGGL((k_part_scatter<D, CH>), grid, block, scatter_lds, stream, (const D *)digits, n, nparts, fbits, lidx, \
-                       pchunk_len, bh, part_base, parted)
-            if (d16 && !big_chunk) GMSM_SCATTER(uint16_t, PART_CHUNK);
-            else if (d16) GMSM_SCATTER(uint16_t, PART_CHUNK_BIG);
-            else if (!big_chunk) GMSM_SCATTER(uint32_t, PART_CHUNK);
-            else GMSM_SCATTER(uint32_t, PART_CHUNK_BIG);
-#undef GMSM_SCATTER
-        }
-        // the partition's references stay in registers between the two passes: 24 per thread (stage_cap <= 24576), else 40
-        if (stage_cap <= 24u * 1024u)
-            hipLaunchKernelGGL(k_fine_sort<24>, dim3(nparts, nw), dim3(1024), ((size_t)4 << fbits) + (size_t)stage_cap * 4, stream,
-                               parted, n, NB, fbits, lidx, part_base, sorted, starts, stage_cap);
-        else
-            hipLaunchKernelGGL(k_fine_sort<40>, dim3(nparts, nw), dim3(1024), ((size_t)4 << fbits) + (size_t)stage_cap * 4, stream,
-                               parted, n, NB, fbits, lidx, part_base, sorted, starts, stage_cap);
-        // partitions beyond the staging slots (crowded buckets, narrow top windows): sorted by many workgroups each. A run of at
-        // most stage_cap entries per window cannot have one: no launches (14 us of a 0.4 ms call)
-        if (n > stage_cap) {
-            hipLaunchKernelGGL(k_heavy_hist, dim3(heavy_wg), dim3(1024), (size_t)4 << fbits, stream, parted, n, nw, nparts, fbits, lidx,
-                               part_base, (const HeavyPart *)hparts, (const uint32_t *)hcount, hcap, scap, subhist);
-            hipLaunchKernelGGL(k_heavy_scan, dim3(std::min<uint32_t>(hcap, 64u), nw), dim3(1024), (size_t)4 << fbits, stream, nparts, NB, fbits,
-                               part_base, (const HeavyPart *)hparts, (const uint32_t *)hcount, hcap, scap, subhist, starts);
-            hipLaunchKernelGGL(k_heavy_place, dim3(heavy_wg), dim3(1024), (size_t)4 << fbits, stream, parted, n, nw, nparts, fbits, lidx,
-                               part_base, (const HeavyPart *)hparts, (const uint32_t *)hcount, hcap, scap, (const uint32_t *)subhist, sorted);
-        }
-        // ---- 2. bucket accumulation, 3. fix-up, 4. bucket reduction: for the windows [k0, k0 + nk) of the launch - all of
-        // them, or (GMSM_OPT_SPLIT, experiment) two groups: the fix-up and reduction of the first group run on the merge stream
-        // beside the accumulation of the second. Every array is window-major, so a group is the same kernels over shifted
-        // base pointers; each group has its own long-chain counter and its own half of the list.
-        if (forked) {
-            HIP_TRY(hipStreamWaitEvent(stream, ws.ev_conv, 0));  // the rewritten bases are complete
-            ws.conv_pending = false;
-        }
-        const auto accumulate = [&](uint32_t k0, uint32_t nk, hipStream_t st) {
-            const uint32_t *st_g = starts + (size_t)k0 * (NB + 1);
-            const uint32_t *sorted_g = sorted + (size_t)k0 * n;
-            char *buckets_g = buckets + (size_t)k0 * NB * REC, *part_g = seg_partials + (size_t)k0 * qa.tpw * 2 * REC;
-            if (shared)
-                hipLaunchKernelGGL((k_accumulate_seg<U, true>), dim3((qa.tpw + 255) / 256, nk), dim3(256), 0, st, upoints, n, NB,
-                                   qa.seg, st_g, sorted_g, buckets_g, part_g, seg_flags + (size_t)k0 * qa.tpw, seg_bucket + (size_t)k0 * qa.tpw,
-                                   qa.tpw, (uint32_t)n_points, (uint32_t)resident->n);
-            else
-                hipLaunchKernelGGL((k_accumulate_seg<U, false>), dim3((qa.tpw + 255) / 256, nk), dim3(256), 0, st, upoints, n, NB,
-                                   qa.seg, st_g, sorted_g, buckets_g, part_g, seg_flags + (size_t)k0 * qa.tpw, seg_bucket + (size_t)k0 * qa.tpw,
-                                   qa.tpw, 0u, 0u);
-        };
-        const auto fixup_and_reduce = [&](uint32_t k0, uint32_t nk, size_t list_off, hipStream_t st, bool mark) {
-            const uint32_t *st_g = starts + (size_t)k0 * (NB + 1);
-            char *buckets_g = buckets + (size_t)k0 * NB * REC, *part_g = seg_partials + (size_t)k0 * qa.tpw * 2 * REC;
-            const uint32_t *flags_g = seg_flags + (size_t)k0 * qa.tpw, *pb_g = seg_bucket + (size_t)k0 * qa.tpw;
-            uint32_t *cnt_g = long_flag + k0;  // k_part_rowscan zeroed every window's slot
-            LongChain *list_g = long_list + list_off;
-            uint32_t *done_g = piece_done + list_off;
-            void *sums_g = (char *)piece_sums + list_off * REC;
-            if (shared && n / NB >= 2 * (size_t)qa.seg)  // buckets of several threads' worth of entries (dense chains): one thread per bucket
-                hipLaunchKernelGGL((k_fixup_bucket<OpsSerial>), dim3((NB + 255) / 256, nk), dim3(256), 0, st, NB, st_g, qa.seg,
-                                   (const void *)part_g, qa.tpw, (void *)buckets_g, cnt_g, list_g, done_g, FIX_MAXWALK);
-            else if constexpr (FIXUP_QUAD)
-                hipLaunchKernelGGL((k_fixup_seg_q<U>), dim3((qa.tpw + 63) / 64, nk), dim3(256), 128 * sizeof(QRec<U>), st, NB,
-                                   (const void *)part_g, flags_g, pb_g, qa.tpw, (void *)buckets_g, cnt_g, list_g, done_g, FIX_MAXWALK, st_g, qa.seg);
-            else
-                hipLaunchKernelGGL((k_fixup_seg<OpsSerial>), dim3((qa.tpw + 255) / 256, nk), dim3(256), 0, st, NB, part_g, flags_g, pb_g,
-                                   qa.tpw, buckets_g, cnt_g, list_g, done_g, FIX_MAXWALK, st_g, qa.seg);
-            hipLaunchKernelGGL((k_fixup_long<U>), dim3(2 * ctx.num_cus), dim3(256), 128 * sizeof(QRec<U>), st, NB, part_g, pb_g, qa.tpw,
-                               buckets_g, (const uint32_t *)cnt_g, (const LongChain *)list_g, done_g, sums_g, st_g, qa.seg);
-            // ---- bucket reduction -> window totals (empty buckets are never written: the reduction consults starts[])
-            if (mark) timer.mark(T_REDUCE, st);
-            if (!buckets_only) enqueue_reduce_kernels(ctx, ws, q, T, buckets_g, st_g, nk, NB, st, k0, planes);
-        };
-        timer.mark(T_ACCUMULATE, stream);
-        if (!split) {
-            accumulate(0, nw, stream);
-            timer.mark(T_FIXUP, stream);
-            fixup_and_reduce(0, nw, 0, stream, true);
-        } else {
-            const uint32_t ha = nw / 2;
-            if ((rc = ws.side_stream(ws.mstream))) return rc;
-            accumulate(0, ha, stream);
-            HIP_TRY(hipEventRecord(ws.ev_buckets, stream));
-            HIP_TRY(hipStreamWaitEvent(ws.mstream, ws.ev_buckets, 0));
-            fixup_and_reduce(0, ha, 0, ws.mstream, false);
-            HIP_TRY(hipEventRecord(ws.ev_merged, ws.mstream));
-            accumulate(ha, nw - ha, stream);
-            timer.mark(T_FIXUP, stream);
-            fixup_and_reduce(ha, nw - ha, list_cap / 2, stream, true);
-            HIP_TRY(hipStreamWaitEvent(stream, ws.ev_merged, 0));
-        }
-        if (!buckets_only && nwd > nw)
-            hipLaunchKernelGGL((k_fill_infinity<Ext>), dim3((nwd - nw + 63) / 64), dim3(64), 0, stream, ws.totals.ptr, nw, nwd - nw);
-        timer.mark(T_END, stream);
-        HIP_TRY(hipGetLastError());
-        if (planes) {  // k_plane_sums wrote ws.pinned itself: nothing to copy
-            ws.plane_np = plane_np;
-            ws.plane_log2L = q.log2L;
-            g_plane_runs.fetch_add(1, std::memory_order_relaxed);
-        } else if (!buckets_only) {
-            if (d_out)
-                HIP_TRY(hipMemcpyAsync(d_out, ws.totals.ptr, (size_t)nwd * sizeof(Ext), hipMemcpyDeviceToDevice, stream));
-            else
-                HIP_TRY(hipMemcpyAsync(ws.pinned, ws.totals.ptr, (size_t)nwd * sizeof(Ext), hipMemcpyDeviceToHost, stream));
-        }
-        if ((rc = end_use(ws, stream))) return rc;
-        ws.pending_timed = timer.on;
-        return GMSM_OK;
-    }
-
-    // quads of k_reduce2_q: a power of two, at least 2, that holds the nlast results of the last combine level
-    static uint32_t reduce2_active(uint32_t nlast) {
-        uint32_t active = 2;
-        while (active < nlast) active <<= 1;
-        return active;
-    }
-    // gmsm_debug_reduce_shape: what the reduction of nw bucket sets of NB buckets is launched as under the current options -
-    // log2L, nblocks1, nblocks2, the (first) combine kernel (1 k_combine_q, 2 k_combine_we), the serial kernel (0 one lane,
-    // 1 quads), the quads of k_reduce2_q. (The number of entries only shapes the accumulation.)
-    static void reduce_shape(const Context &ctx, uint32_t nw, uint32_t NB, uint32_t out[6]) {
-        const Geometry q = plan_geometry(ctx, nw, NB, NB);
-        out[0] = q.log2L;
-        out[1] = q.nblocks1;
-        out[2] = q.nblocks2;
-        out[3] = use_combine_we(ctx, q.nblocks1 * nw) ? 2u : 1u;
-        out[4] = SERIAL_QUAD ? 1u : 0u;
-        out[5] = reduce2_active(q.nblocks2 ? q.nblocks2 : q.nblocks1);
-    }
-
-    // The three kernels of the bucket reduction: buckets (nw x NB lazy records; starts == nullptr: every record is
-    // stored, infinity as zz = 0) -> ws.totals. Scratch: ws.red_pre, ws.partials.
-    static void enqueue_reduce_kernels(Context &ctx, Workspace &ws, const Geometry &q, uint32_t T, const void *buckets,
-                                       const uint32_t *starts, uint32_t nw, uint32_t NB, hipStream_t stream,
-                                       uint32_t k0 = 0 /* first window of a group: offsets into the scratch and the totals */,
-                                       bool planes = false /* stop at the plane sums, written to ws.pinned (k0 == 0) */) {
-        constexpr size_t RECB = sizeof(typename OpsSerial::Mem);
-        void *red_pre = (char *)ws.red_pre.ptr + (size_t)k0 * T * 2 * RECB;
-        void *partials = (char *)ws.partials.ptr + (size_t)k0 * q.nblocks1 * 2 * RECB;  // (groups only with two levels)
-        void *totals = (char *)ws.totals.ptr + (size_t)k0 * sizeof(Ext);
-        // level 1 leaves S_blk already multiplied by the width of the level-2 spans (an otherwise idle quad doubles it
-        // log2span times while the trees run): level 2 then has no serial doubling tail
-        const uint32_t prescale = q.log2span;
-        if constexpr (SERIAL_QUAD)
-            hipLaunchKernelGGL((k_reduce_serial_q<U, SERIAL_Q_QUADS>), dim3((T + SERIAL_Q_QUADS - 1) / SERIAL_Q_QUADS, nw), dim3(4 * SERIAL_Q_QUADS),
-                               3 * SERIAL_Q_QUADS * sizeof(QRec<U>), stream, buckets, NB, q.log2L, T, starts, red_pre);
-        else
-            hipLaunchKernelGGL((k_reduce_serial<OpsSerial>), dim3((T + 255) / 256, nw), dim3(256), 0, stream, buckets, NB,
-                               q.log2L, T, starts, red_pre);
-        if constexpr (COMBINE_WE) {
-            if (planes) {  // GMSM_OPT_REDUCE_TAIL: sums only, the host fold applies the weights (fold_planes)
-                uint32_t h = 0;
-                while ((1u << h) < q.nblocks1) ++h;
-                const uint32_t quads = std::min(64u, std::max(16u, (1u << h) / 2));  // a step has at most 2^h / 2 additions
-                hipLaunchKernelGGL((k_combine_we<U, true, true>), dim3(q.nblocks1, nw), dim3(4 * COMBINE_N),
-                                   (2 * COMBINE_N + 1) * sizeof(QRec<U>), stream, q.log2L, ws.partials.ptr, 0u, (const void *)red_pre, T);
-                hipLaunchKernelGGL((k_plane_sums<U, true>), dim3(nw, 8), dim3(4 * quads), ((size_t)1 << h) * sizeof(QRec<U>), stream,
-                                   (const void *)ws.partials.ptr, q.nblocks1, h, ws.pinned);
-                return;
-            }
-        }
-        // one combine level: `pairs` (S, W) pairs per window, each the sum of 2^l2 buckets (S prescaled by the caller's
-        // factor when l2 == 0) -> `blocks` pairs per window
-        const auto combine = [&](const void *in, uint32_t pairs, void *out, uint32_t blocks, uint32_t l2, uint32_t pre) {
-            if constexpr (COMBINE_WE) {
-                if (use_combine_we(ctx, blocks * nw)) {
-                    hipLaunchKernelGGL((k_combine_we<U, true>), dim3(blocks, nw), dim3(4 * COMBINE_N),
-                                       (2 * COMBINE_N + 1) * sizeof(QRec<U>), stream, l2, out, pre, in, pairs);
-                    return;
-                }
-            }
-            hipLaunchKernelGGL((k_combine_q<U, true, COMBINE_N>), dim3(blocks, nw), dim3(4 * COMBINE_N),
-                               (2 * COMBINE_N + 1) * sizeof(QRec<U>), stream, l2, out, pre, in, pairs);
-        };
-        combine(red_pre, T, partials, q.nblocks1, q.log2L, prescale);
-        const void *last = partials;
-        uint32_t nlast = q.nblocks1, rest = q.log2span - prescale;
-        if (q.nblocks2) {
-            // second combine: its input pairs carry S already multiplied by their own span (the prescale above), so the
-            // pairs count as single buckets (L = 1); its S_blk is doubled log2 N more times for the last level
-            constexpr size_t REC = sizeof(typename OpsSerial::Mem);
-            void *out2 = (char *)partials + (size_t)nw * q.nblocks1 * 2 * REC;
-            uint32_t lgN = 0;
-            for (size_t t = COMBINE_N; t > 1; t >>= 1) ++lgN;
-            combine(partials, q.nblocks1, out2, q.nblocks2, 0, lgN);
-            last = out2;
-            nlast = q.nblocks2;
-            rest = 0;
-        }
-        const uint32_t active = reduce2_active(nlast);
-        hipLaunchKernelGGL((k_reduce2_q<U, true>), dim3(nw), dim3(4 * active), 2 * active * sizeof(QRec<U>), stream, last, nlast,
-                           rest, active, totals);
-        (void)ctx;
-    }
-
-    // The reduction alone, over bucket sums that a multi-range call has merged (every record stored): totals -> ws.pinned.
-    static int enqueue_reduce(Context &ctx, Workspace &ws, const void *buckets, const WindowPlan &plan, size_t n_for_geometry,
-                              hipStream_t stream) {
-        const uint32_t nw = bucket_sets(plan), nwd = plan.nwin_local, NB = plan.nbuckets;
-        constexpr size_t REC = sizeof(typename OpsSerial::Mem);
-        const Geometry q = plan_geometry(ctx, nw, n_for_geometry, NB);
-        const uint32_t T = (uint32_t)(((size_t)NB + ((size_t)1 << q.log2L) - 1) >> q.log2L);
-        int rc;
-        ws.plane_np = 0;
-        if ((rc = ws.partials.ensure((size_t)nw * (q.nblocks1 + q.nblocks2) * 2 * REC))) return rc;
-        if ((rc = ws.red_pre.ensure((size_t)nw * T * 2 * REC))) return rc;
-        if ((rc = ws.totals.ensure((size_t)nwd * sizeof(Ext)))) return rc;
-        if ((rc = ws.ensure_pinned((size_t)nwd * sizeof(Ext)))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_combine_q<U, true, COMBINE_N>, (int)((2 * COMBINE_N + 1) * sizeof(QRec<U>))))) return rc;
-        if constexpr (COMBINE_WE)
-            if ((rc = ctx.allow_lds((const void *)k_combine_we<U, true>, (int)((2 * COMBINE_N + 1) * sizeof(QRec<U>))))) return rc;
-        if constexpr (SERIAL_QUAD)
-            if ((rc = ctx.allow_lds((const void *)k_reduce_serial_q<U, SERIAL_Q_QUADS>, (int)(3 * SERIAL_Q_QUADS * sizeof(QRec<U>))))) return rc;
-        if ((rc = ctx.allow_lds((const void *)k_reduce2_q<U, true>, (int)(2 * RED2_TPB * sizeof(QRec<U>))))) return rc;
-        enqueue_reduce_kernels(ctx, ws, q, T, buckets, nullptr, nw, NB, stream);
-        if (nwd > nw)
-            hipLaunchKernelGGL((k_fill_infinity<Ext>), dim3((nwd - nw + 63) / 64), dim3(64), 0, stream, ws.totals.ptr, nw, nwd - nw);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(ws.pinned, ws.totals.ptr, (size_t)nwd * sizeof(Ext), hipMemcpyDeviceToHost, stream));
-        return GMSM_OK;
     }
 
     // ---- N3: fixed-base batch scalar multiplication / batch normalisation (gmsm_fixedbase.h; the table is GroupHost's) ----
@@ -925,7 +118,6 @@ struct Group : GroupHost<F_, FrP_> {
         HIP_TRY(hipGetLastError());
         if ((rc = normalize_records(ws, n, d_out))) return rc;
         HIP_TRY(hipStreamSynchronize(ws.stream));  // `table` (pageable host memory) must outlive the copy
-        (void)ctx;
         return GMSM_OK;
     }
 
@@ -1051,7 +243,6 @@ struct Group : GroupHost<F_, FrP_> {
             HIP_TRY(hipStreamSynchronize(stream));
         }
         out->n = n;
-        (void)ctx;
         return GMSM_OK;
     }
 
@@ -1155,7 +346,6 @@ struct Group : GroupHost<F_, FrP_> {
     // c-bit decomposition, so that the digits of ALL windows index one bucket set - one reduction of 2^(c-1) buckets
     // instead of nwin of them, which in turn lets c grow (fewer windows = fewer additions). 288 GB of HBM pay for it:
     // nwin copies of the bases (BN254 G1, 2^20 points, c = 19: 14 x 64 MiB).
-    static uint32_t bucket_sets(const WindowPlan &plan) { return plan.shared ? 1u : plan.nwin_local; }
     // GMSM_OPT_TABLES: 0 = never, 1 (default) = the measured range of call sizes, 2 = whenever the handle has tables (tests)
     static bool tables_serve(size_t n_registered, size_t n_call) {
         const unsigned mode = options().tables.load(std::memory_order_relaxed);
@@ -1187,8 +377,6 @@ struct Group : GroupHost<F_, FrP_> {
         }
         return make_plan(choose_c(FR_BITS, AFF_BYTES, n), 0, 1);
     }
-    // widths k_decompose_glv is instantiated for
-    static bool glv_width_built(unsigned c) { return (c >= 10 && c <= 18) || c == 20; }
     // Default table width for n registered points, from sweeps of every group over 2^13..2^21 with the width forced
     // (tools/tables_sweep.py, profiles/r03_tables.log). What moves it away from the plain path's width: the shared set
     // holds nwin * n entries, so (a) a wider window pays twice - fewer slabs to add AND shorter chains of partial sums
@@ -1277,7 +465,6 @@ struct Group : GroupHost<F_, FrP_> {
                 clear_last_error();
             }
         }
-        (void)ctx;
         return GMSM_OK;
     }
 
@@ -1508,8 +695,11 @@ struct Group : GroupHost<F_, FrP_> {
         for (unsigned r = 0; r * per < n; ++r) {
             const size_t lo = (size_t)r * per, len = std::min(per, n - lo);
             const void *dp = d_points ? (const char *)d_points + lo * AFF_BYTES : nullptr;
-            if ((rc = enqueue_window_sums(ctx, ws, dp, (const char *)d_scalars + lo * SCALAR_BYTES, len, plan, ws.stream, resident,
-                                          nullptr, lo, /*buckets_only=*/true, /*time_range=*/prof)))
+            RunRequest rq;
+            rq.resident_offset = lo;
+            rq.buckets_only = true;
+            rq.time_range = prof;
+            if ((rc = enqueue_window_sums(ctx, ws, dp, (const char *)d_scalars + lo * SCALAR_BYTES, len, plan, ws.stream, resident, rq)))
                 return rc;
             if (prof && ws.pending_timed) {
                 HIP_TRY(wait_stream(ws.stream));
@@ -1534,7 +724,9 @@ struct Group : GroupHost<F_, FrP_> {
         WindowPlan plan = plan_for(resident, n);
         if (n > max_run_points(plan)) plan = make_plan(choose_c(FR_BITS, AFF_BYTES, n), 0, 1);  // one run per ticket: plain path
         const unsigned c = plan.c;
-        int rc = enqueue_window_sums(ctx, ws, nullptr, d_scalars, n, plan, ws.stream, resident, nullptr, 0, false, false, TAIL_AUTO);
+        RunRequest rq;
+        rq.tail_mode = TAIL_AUTO;
+        int rc = enqueue_window_sums(ctx, ws, nullptr, d_scalars, n, plan, ws.stream, resident, rq);
         if (rc) return rc;
         ws.pending_c = c;
         ws.pending_nw = plan.nwin_total;
@@ -1543,7 +735,6 @@ struct Group : GroupHost<F_, FrP_> {
     static int multiexp_collect(Workspace &ws, J *out) {
         return collect_folded(ws, ws.stream, ws.pending_c, ws.pending_nw, out);
     }
-
 
     // Number of point ranges a host-buffer MultiExp is cut into so that the H2D copy of range k+1 runs under the
     // pipeline of range k (two workspaces, two streams). Round 2 reduced every range on its own and added the totals on
@@ -1628,6 +819,9 @@ struct Group : GroupHost<F_, FrP_> {
             Workspace &ws = *w[r % nws];
             const size_t lo = cut[r], len = cut[r + 1] - lo;
             const void *dp = nullptr;
+            RunRequest rq;
+            rq.resident_offset = resident_base + lo;
+            rq.buckets_only = nr > 1;  // (one range: the whole pipeline, totals in ws.pinned)
             // hipMemcpyAsync from pageable memory returns when the caller's buffer has been consumed; the kernels
             // queued behind it do not wait for the host, so range k computes while range k+1 is being copied
             if ((rc = ws.h2d_scalars.ensure(len * SCALAR_BYTES))) break;
@@ -1646,7 +840,7 @@ struct Group : GroupHost<F_, FrP_> {
                 dp = ws.h2d_points.ptr;
             }
             if (nr == 1) {
-                rc = enqueue_window_sums(ctx, ws, dp, ws.h2d_scalars.ptr, len, plan, ws.stream, resident, nullptr, resident_base + lo);
+                rc = enqueue_window_sums(ctx, ws, dp, ws.h2d_scalars.ptr, len, plan, ws.stream, resident, rq);
                 break;
             }
             // the buckets of the range this workspace ran two ranges ago must have been merged before they are overwritten
@@ -1656,9 +850,7 @@ struct Group : GroupHost<F_, FrP_> {
                 rc = fail(GMSM_ERR_DEVICE, std::string("hipStreamWaitEvent: ") + hipGetErrorString(he));
                 break;
             }
-            if ((rc = enqueue_window_sums(ctx, ws, dp, ws.h2d_scalars.ptr, len, plan, ws.stream, resident, nullptr,
-                                          resident_base + lo, /*buckets_only=*/true)))
-                break;
+            if ((rc = enqueue_window_sums(ctx, ws, dp, ws.h2d_scalars.ptr, len, plan, ws.stream, resident, rq))) break;
             if (nws == 2) {
                 he = hipEventRecord(ws.ev_buckets, ws.stream);
                 if (he == hipSuccess) he = hipStreamWaitEvent(ms, ws.ev_buckets, 0);

@@ -69,7 +69,9 @@ struct VTableOf {
         // (Workspace::last_use, honoured by whoever leases the workspace next), not by the lease
         GMSM_LEASE_OR_FAIL(lease, ctx);
         Workspace *ws = lease.w;
-        int rc = G::enqueue_window_sums(ctx, *ws, d_points, d_scalars, n, plan, stream, resident.get(), d_out_xyzz);
+        RunRequest rq;
+        rq.d_out = d_out_xyzz;
+        int rc = G::enqueue_window_sums(ctx, *ws, d_points, d_scalars, n, plan, stream, resident.get(), rq);
         ws->bases_ref = resident;             // alive until the next call on this workspace replaces it
         ws->uncollected = ws->pending_timed;  // nobody waits for this call: its stage events are read by the next one
         ws->pending_timed = false;
@@ -170,7 +172,23 @@ struct VTableOf {
         const WindowPlan p = G::plan_for(nullptr, n);
         *c = p.c, *nwin = p.nwin_total, *entries_per_point = p.glv ? 2u : 1u, *fused = 0u;
     }
-    static void reduce_shape(const Context &ctx, uint32_t nw, uint32_t nbuckets, uint32_t out[6]) { G::reduce_shape(ctx, nw, nbuckets, out); }
+    static void reduce_shape(const Context &ctx, uint32_t nw, uint32_t nbuckets, uint32_t out[6]) { G::reduce_shape(ctx.num_cus, nw, nbuckets, out); }
+    // gmsm_debug_run_layout: Pipeline::plan_run, no device; flags = resident | d_out << 1 | buckets_only << 2 | tail_mode << 3
+    static int run_layout(int num_cus, size_t n, unsigned c, unsigned win_first, unsigned win_stride, bool glv, bool shared,
+                          unsigned flags, uint64_t *out) {
+        if (glv && !G::glv_width_built(c)) return fail(GMSM_ERR_ARG, "gmsm_debug_run_layout: no GLV decomposition of this width");
+        WindowPlan plan = glv ? G::make_plan_glv(c, win_first, win_stride) : G::make_plan(c, win_first, win_stride);
+        plan.shared = shared ? 1 : 0;
+        RunRequest rq;
+        rq.d_out = (flags & 2u) ? out : nullptr;  // (only its presence shapes the layout)
+        rq.buckets_only = (flags & 4u) != 0;
+        rq.tail_mode = (int)((flags >> 3) & 3u);
+        if (plan.nwin_local == 0) return fail(GMSM_ERR_ARG, "gmsm_debug_run_layout: no window in this piece");
+        const typename G::RunLayout layout = G::plan_run(num_cus, plan, n, (flags & 1u) != 0, rq);
+        if (layout.error) return fail(GMSM_ERR_ARG, layout.error);
+        G::flatten(num_cus, layout, out);
+        return GMSM_OK;
+    }
     static void fold_planes(const uint64_t *planes, unsigned c, unsigned nwin, unsigned log2L, unsigned nhigh, uint64_t *out_jac) {
         typename G::J j = G::fold_planes(reinterpret_cast<const typename G::Ext *>(planes), c, nwin, log2L, nhigh);
         memcpy(out_jac, &j, sizeof j);
@@ -711,7 +729,7 @@ struct VTableOf {
             GMSM_VT(decode_raw), GMSM_VT(validate_points), GMSM_VT(decode_compressed), GMSM_VT(encode_compressed);
             GMSM_VT(fft_domain_new), GMSM_VT(fft_run), GMSM_VT(fft_bit_reverse);
             GMSM_VT(precompute_tables), GMSM_VT(tables_serve), GMSM_VT(shard_piece), GMSM_VT(host_piece_ranges);
-            GMSM_VT(debug_glv_split), GMSM_VT(plan_info), GMSM_VT(reduce_shape), GMSM_VT(fold_planes);
+            GMSM_VT(debug_glv_split), GMSM_VT(plan_info), GMSM_VT(reduce_shape), GMSM_VT(run_layout), GMSM_VT(fold_planes);
             GMSM_VT(poly_eval), GMSM_VT(poly_div), GMSM_VT(kzg_open);
             if constexpr (IS_G1) GMSM_VT(to_lagrange);  // the three G1-only members stay null for the G2 groups
             GMSM_VT(fflonk_next_divisor), GMSM_VT(open_check), GMSM_VT(fflonk_fold);

@@ -561,6 +561,15 @@ int gmsm_debug_reduce_shape(int group, uint32_t nw, uint32_t nbuckets, uint32_t 
  * sum_l 2^(log2L + l) m_l + sum_l 2^(log2L + 6 + l) h_l), infinity as (1, 1, 0) */
 int gmsm_debug_fold_planes(int group, unsigned c, unsigned nwin, unsigned log2L, unsigned nblocks1, const uint64_t *planes,
                            uint64_t *out_jac);
+/* what one run of the sorted pipeline derives on the host before it touches the device, no device needed: the layout of a
+ * run over n points of the windows win_first, win_first + win_stride, ... of the c-bit decomposition (glv: of the half
+ * scalars; shared: the one bucket set of window tables) on a device of num_cus compute units, under the current options.
+ * flags = registered bases | totals stay on the device << 1 | stop after the fix-up << 2 | what the caller takes << 3 (0 window
+ * totals, 1 plane sums when forced, 2 plane sums whenever they pay). out = GMSM_RUN_LAYOUT_WORDS integers, named in order by
+ * "fields" of tests/golden/pipeline_layout.json; a run the pipeline would refuse is refused here with the same text. */
+#define GMSM_RUN_LAYOUT_WORDS 51
+int gmsm_debug_run_layout(int group, int num_cus, size_t n, unsigned c, unsigned win_first, unsigned win_stride, int glv, int shared,
+                          unsigned flags, uint64_t *out);
 unsigned long gmsm_debug_plane_runs(void); /* pipeline runs whose reduction ended in k_plane_sums so far (tests) */
 
 /* ---- utilities ---- */
@@ -600,8 +609,8 @@ enum gmsm_option {
                                  that neither force a window width nor are served by window tables): 0 (default) = on, width
                                  by size; 1 = off (the sorted pipeline for every size); 2..7 = on with this window width */
     GMSM_OPT_SMALL_MAX = 7,   /* largest call the fused small-n kernel takes (0 = the measured default) */
-    GMSM_OPT_SPLIT = 8,       /* experiment (default 0 = off): a call's windows in two groups, the fix-up + reduction of the first on a
-                                 second stream beside the accumulation of the second (measured: profiles/r05_split_groups.log) */
+    GMSM_OPT_SPLIT = 8,       /* retired: still accepted and read back, no effect. It ran a call's windows as two groups on two streams;
+                                 no gain (profiles/r05_split_groups.log), and the code is gone */
     GMSM_OPT_GLV = 9,         /* GLV half scalars (ecc/utils.go:62-170; s P = k1 P + k2 phi(P), half the windows and half the host
                                  fold for the same group element): 0 never; 1 (default) in the fused small-n kernel and, for
                                  bases taken anew, in the sorted pipeline at the sizes where it was measured ahead (2^13..2^20

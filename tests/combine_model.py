@@ -233,7 +233,7 @@ def reduce2_active(nlast):
 
 
 def reduce_window(grp, B, stored, log2L, three, we):
-    """Group::enqueue_reduce_kernels for one bucket set: the serial level with L = 2^log2L, one combine (two with `three`),
+    """Pipeline::enqueue_reduce_kernels for one bucket set: the serial level with L = 2^log2L, one combine (two with `three`),
     k_reduce2_q. B[j]: bucket sums in grp (None = infinity), stored[j]: the record exists. Returns (total, info) with
     info = dict(S=[S_t], W=[W_t]) of the serial level."""
     NB, L, N = len(B), 1 << log2L, COMBINE_N

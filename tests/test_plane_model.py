@@ -27,7 +27,7 @@ def direct(S, W, L):
 
 def quads_for(T):
     H = (-(-T // pm.N) - 1).bit_length()
-    return min(64, max(16, (1 << H) // 2))  # Group::enqueue_reduce_kernels
+    return min(64, max(16, (1 << H) // 2))  # Pipeline::enqueue_reduce_kernels
 
 
 @pytest.mark.parametrize("zero_S", [False, True])

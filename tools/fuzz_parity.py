@@ -37,10 +37,9 @@ def main():
     while time.time() - t0 < budget:
         n = int(rng.choice([rng.integers(1, 64), rng.integers(64, 5000), rng.integers(5000, nmax)]))
         kind = int(rng.integers(0, 11))
-        # the fused small-n kernel on / off / forced widths and sizes; the experimental window-group split
+        # the fused small-n kernel on / off / forced widths and sizes
         gm.set_option("small_bits", int(rng.choice([0, 0, 0, 1, 4, 5, 6, 7])))
         gm.set_option("small_max", int(rng.choice([0, 0, 300, 16384])))
-        gm.set_option("split", int(rng.choice([0, 0, 0, 1])))
         # round 6: GLV half scalars never / by the measured table / always, the fused kernel's bucket phase by size / one lane / quads
         gm.set_option("glv", int(rng.choice([0, 1, 1, 2])))
         gm.set_option("small_quad", int(rng.choice([0, 0, 1, 2])))
@@ -120,7 +119,7 @@ def main():
             if err is not None or not (back == both).all():
                 bad += 1
                 print("COMPRESSED ROUND TRIP MISMATCH", dict(n=n, err=err), flush=True)
-    for k in ("small_bits", "small_max", "split", "small_quad", "poly_lane_bits", "reduce_shape"):
+    for k in ("small_bits", "small_max", "small_quad", "poly_lane_bits", "reduce_shape"):
         gm.set_option(k, 0)
     gm.set_option("glv", 1)
     for h in handles:
