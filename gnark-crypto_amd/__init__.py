@@ -10,5 +10,5 @@ from . import fft  # noqa: F401  (fr/fft mirror: fft.NewDomain, fft.DIT / fft.DI
 from . import kzg  # noqa: F401  (kzg mirror: kzg.Open, kzg.BatchOpenSinglePoint, kzg.PolyEval, kzg.DividePolyByXMinusA, kzg.ToLagrangeG1)
 from . import shplonk  # noqa: F401  (shplonk mirror: shplonk.BatchOpen, shplonk.OpenW, shplonk.OpenWPrime)
 from . import fflonk  # noqa: F401  (fflonk mirror: fflonk.Fold, fflonk.FoldAndCommit, fflonk.BatchOpen, fflonk.OpenW, fflonk.OpenWPrime)
-from . import iop  # noqa: F401  (fr/iop mirror: iop.BuildRatioCopyConstraint, iop.BuildRatioShuffledVectors; fr.BatchInvert as iop.BatchInvert; iop.Polynomial with its basis changes and Evaluate, iop.DivideByXMinusOne)
+from . import iop  # noqa: F401  (fr/iop mirror: iop.BuildRatioCopyConstraint, iop.BuildRatioShuffledVectors; fr.BatchInvert as iop.BatchInvert; iop.Polynomial with its basis changes and Evaluate, iop.DivideByXMinusOne, iop.Evaluate over iop.Program)
 from . import mpcsetup  # noqa: F401  (mpcsetup mirror: mpcsetup.UpdateMonomialsG1/G2, mpcsetup.ScaleG1/G2, mpcsetup.BatchScaleG1/G2, mpcsetup.linearCombinationsG1/G2)

@@ -808,6 +808,12 @@ struct GroupVTable {
                         uint64_t *out_values);
     int (*iop_quotient)(Context &ctx, FftDomain *small, FftDomain *big, const uint64_t *a, const void *d_a, int layout, size_t shift,
                         hipStream_t stream, uint64_t *out, void *d_out);
+    // iop.Evaluate of a straight-line program (gmsm_iop_expr.h). The engine has validated the program (nregs = the registers it
+    // uses), reduced offsets[j] = rho_j shifts[j] mod len and refused every overlap but the in-place one; d = the domain of a
+    // program with POINT (its cardinality is len), else null.
+    int (*iop_expr)(Context &ctx, FftDomain *d, const uint32_t *prog, size_t prog_len, unsigned nregs, const uint64_t *consts, size_t n_consts,
+                    const uint64_t *const *polys, const void *const *d_polys, size_t m, size_t len, const size_t *offsets,
+                    const uint32_t *layouts, int out_layout, hipStream_t stream, uint64_t *out, void *d_out);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

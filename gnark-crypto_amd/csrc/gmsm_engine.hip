@@ -1805,6 +1805,126 @@ GMSM_EXPORT int gmsm_iop_divide_by_x_minus_one(uint64_t domain_small, uint64_t d
                             (hipStream_t)hip_stream, out, d_out);
 }
 
+// ------------------------------------------------------------------ iop.Evaluate of a straight-line program (gmsm_iop_expr.h)
+// The program's checks, in instruction order, so that the kernel never sees a bad one: every text names the instruction.
+// *nregs = the registers the program uses (a read is of a register written before, so the writes bound them).
+static int expr_validate(const char *E, const uint32_t *prog, size_t prog_len, size_t m, size_t n_consts, bool has_domain, unsigned *nregs,
+                         bool *has_point) {
+    if (prog_len == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": empty program");
+    if (prog_len > GMSM_EXPR_MAX_INSNS)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": the program has " + std::to_string(prog_len) + " instructions, more than " +
+                                      std::to_string(GMSM_EXPR_MAX_INSNS));
+    uint32_t written = 0;
+    *nregs = 0, *has_point = false;
+    for (size_t pc = 0; pc < prog_len; ++pc) {
+        const uint32_t ins = prog[pc];
+        const unsigned op = ins & 0xff, dst = (ins >> 8) & 0xff, a = (ins >> 16) & 0xff, b = ins >> 24;
+        const std::string at = std::string(E) + ": instruction " + std::to_string(pc) + ": ";
+        auto reads = [&](unsigned reg) {
+            if (reg >= GMSM_EXPR_MAX_REGS) return fail(GMSM_ERR_ARG, at + "register " + std::to_string(reg) + " is not below " + std::to_string(GMSM_EXPR_MAX_REGS));
+            if (!((written >> reg) & 1)) return fail(GMSM_ERR_ARG, at + "reads register " + std::to_string(reg) + " before any instruction wrote it");
+            return (int)GMSM_OK;
+        };
+        int rc = GMSM_OK;
+        switch (op) {
+            case GMSM_EXPR_INPUT:
+                if (a >= m) return fail(GMSM_ERR_ARG, at + "input " + std::to_string(a) + " of " + std::to_string(m));
+                break;
+            case GMSM_EXPR_CONST:
+                if (a >= n_consts) return fail(GMSM_ERR_ARG, at + "constant " + std::to_string(a) + " of " + std::to_string(n_consts));
+                break;
+            case GMSM_EXPR_POINT:
+                if (!has_domain) return fail(GMSM_ERR_ARG, at + "POINT needs a domain (domain == 0)");
+                *has_point = true;
+                break;
+            case GMSM_EXPR_ADD:
+            case GMSM_EXPR_SUB:
+            case GMSM_EXPR_MUL:
+                if ((rc = reads(a)) || (rc = reads(b))) return rc;
+                break;
+            case GMSM_EXPR_NEG:
+                if ((rc = reads(a))) return rc;
+                break;
+            default: return fail(GMSM_ERR_ARG, at + "unknown opcode " + std::to_string(op));
+        }
+        if (dst >= GMSM_EXPR_MAX_REGS) return fail(GMSM_ERR_ARG, at + "register " + std::to_string(dst) + " is not below " + std::to_string(GMSM_EXPR_MAX_REGS));
+        written |= 1u << dst;
+        *nregs = std::max(*nregs, dst + 1);
+    }
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_iop_evaluate_expression(int group, uint64_t domain, const uint32_t *prog, size_t prog_len, const uint64_t *consts,
+                                             size_t n_consts, const uint64_t *const *polys, const void *const *d_polys, size_t m, size_t len,
+                                             const size_t *sizes, const int64_t *shifts, const uint32_t *layouts, int out_layout, void *hip_stream,
+                                             uint64_t *out, void *d_out) {
+    const GroupVTable *vt = fr_vtable(group);
+    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    const char *E = "gmsm_iop_evaluate_expression";
+    if (len == 0) return GMSM_OK;
+    if (m == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": need at least one input (m == 0)");
+    if (m > GMSM_EXPR_MAX_INPUTS) return fail(GMSM_ERR_ARG, std::string(E) + ": " + std::to_string(m) + " inputs, more than " + std::to_string(GMSM_EXPR_MAX_INPUTS));
+    if (n_consts > GMSM_EXPR_MAX_CONSTS)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": " + std::to_string(n_consts) + " constants, more than " + std::to_string(GMSM_EXPR_MAX_CONSTS));
+    if (!prog) return fail(GMSM_ERR_ARG, std::string(E) + ": prog is null");
+    if (n_consts && !consts) return fail(GMSM_ERR_ARG, std::string(E) + ": consts is null");
+    if (!sizes || !shifts) return fail(GMSM_ERR_ARG, std::string(E) + ": sizes and shifts must not be null");
+    int rc = ratio_layouts(E, "layouts", layouts, m);
+    if (rc || (rc = iop_layout(E, out_layout)) || (rc = ratio_pair(E, "polys", "d_polys", polys, d_polys)) ||
+        (rc = ratio_pair(E, "out", "d_out", out, d_out)))
+        return rc;
+    const void *const *in = polys ? (const void *const *)polys : d_polys;
+    for (size_t j = 0; j < m; ++j)
+        if (!in[j]) return fail(GMSM_ERR_ARG, std::string(E) + ": " + (polys ? "polys[" : "d_polys[") + std::to_string(j) + "] is null");
+    unsigned nregs = 0;
+    bool has_point = false, reversed = out_layout == 16;
+    if ((rc = expr_validate(E, prog, prog_len, m, n_consts, domain != 0, &nregs, &has_point))) return rc;
+    std::vector<size_t> offsets(m);
+    for (size_t j = 0; j < m; ++j) {
+        reversed = reversed || layouts[j] == 16;
+        if (sizes[j] == 0 || sizes[j] > len)
+            return fail(GMSM_ERR_ARG, std::string(E) + ": sizes[" + std::to_string(j) + "] = " + std::to_string(sizes[j]) + " is outside [1, len]");
+        if (shifts[j] < 0)
+            return fail(GMSM_ERR_ARG, std::string(E) + ": shifts[" + std::to_string(j) + "] = " + std::to_string(shifts[j]) +
+                                          " is negative (the reference panics on the index)");
+        // rho shift mod len without overflow: both factors are reduced first, and their product is below len^2
+        const size_t rho = len / sizes[j];
+        offsets[j] = (size_t)(((unsigned __int128)(rho % len) * ((uint64_t)shifts[j] % len)) % len);
+    }
+    if ((reversed || has_point) && (len & (len - 1)))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": len must be a power of 2 with a BitReverse layout or a POINT instruction");
+    if (len > ((size_t)1 << 62) / (m * vt->scalar_bytes)) return fail(GMSM_ERR_ARG, std::string(E) + ": m * len does not fit");
+    FftRef d;
+    if (domain != 0) {
+        if (!(d = g_fft.get(domain))) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
+        if ((d->group & ~1) != (group & ~1)) return fail(GMSM_ERR_ARG, std::string(E) + ": the domain is of another curve");
+        if (has_point && ((size_t)1 << d->log2n) != len)
+            return fail(GMSM_ERR_ARG, std::string(E) + ": the domain's cardinality " + std::to_string((size_t)1 << d->log2n) + " is not len " +
+                                          std::to_string(len) + " (POINT is w^i with w = fft.Generator(len))");
+    }
+    // The output may be input j itself when the lane that reads a slot is the lane that writes it; any other shared byte is refused
+    const size_t bytes = len * vt->scalar_bytes;
+    const uintptr_t o = (uintptr_t)(out ? (const void *)out : (const void *)d_out);
+    for (size_t j = 0; j < m; ++j) {
+        const uintptr_t i = (uintptr_t)in[j];
+        if ((out != nullptr) != (polys != nullptr) || !(o < i + bytes && i < o + bytes)) continue;
+        if (o != i) return ratio_aliases(E);
+        if (layouts[j] != (uint32_t)out_layout || offsets[j] != 0)
+            return fail(GMSM_ERR_ARG, std::string(E) + ": the output is input " + std::to_string(j) +
+                                          ", which needs the same layout and no offset (the lane that reads a slot must be the one that writes it)");
+    }
+    Context *ctx;
+    if (d && has_point) rc = enter_on(d->device, &ctx);  // the domain decides the device
+    else rc = enter_owner(d_polys ? d_polys[0] : d_out, &ctx);
+    if (rc) return rc;
+    if (d_polys)
+        for (size_t j = 0; j < m; ++j)
+            if ((rc = check_device_vector(E, ("d_polys[" + std::to_string(j) + "]").c_str(), d_polys[j], ctx->device))) return rc;
+    if ((rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
+    return vt->iop_expr(*ctx, has_point ? d.get() : nullptr, prog, prog_len, nregs, consts, n_consts, polys, d_polys, m, len, offsets.data(), layouts,
+                        out_layout, (hipStream_t)hip_stream, out, d_out);
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {

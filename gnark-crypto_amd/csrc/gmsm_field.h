@@ -198,18 +198,50 @@ GMSM_HD Fp<P> fp_neg(const Fp<P> &x) {
     return z;
 }
 
+// The 32-bit form of the product below, always inlined: for a kernel that cannot afford the call (the call ABI gives the
+// arguments 16 registers, so the second operand of a 12-limb product travels through scratch memory; gmsm_iop_expr.h).
+template <class P>
+GMSM_HD Fp<P> fp_mul_inline(const Fp<P> &x, const Fp<P> &y) {
+    constexpr int N = P::N;
+    uint32_t t[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) t[i] = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const uint32_t yi = y.l[i];
+        uint64_t a = (uint64_t)x.l[0] * yi + t[0];
+        uint32_t A = (uint32_t)(a >> 32);
+        const uint32_t m = (uint32_t)a * P::QINV;
+        uint64_t c = (uint64_t)m * P::Q[0] + (uint32_t)a;
+        uint32_t C = (uint32_t)(c >> 32);
+#pragma unroll
+        for (int j = 1; j < N; ++j) {
+            a = (uint64_t)x.l[j] * yi + t[j] + A;
+            A = (uint32_t)(a >> 32);
+            c = (uint64_t)m * P::Q[j] + (uint32_t)a + C;
+            C = (uint32_t)(c >> 32);
+            t[j - 1] = (uint32_t)c;
+        }
+        t[N - 1] = A + C;  // no-carry condition: cannot overflow
+    }
+    Fp<P> z;
+#pragma unroll
+    for (int i = 0; i < N; ++i) z.l[i] = t[i];
+    fp_reduce_once(z);
+    return z;
+}
+
 // Montgomery product x*y*R^-1 mod q. Two interleaved carry chains per outer iteration (A for x*y_i, C for m*q),
 // each inner step is a 32x32 multiply plus two 32-bit addends, which never overflows 64 bits.
 template <class P>
 GMSM_MUL_HD Fp<P> fp_mul(const Fp<P> x, const Fp<P> y) {
-    constexpr int N = P::N;
 #if !defined(__HIP_DEVICE_COMPILE__)
     // host (window fold, FromJacobian, base generator): the no-carry CIOS of the reference (element_purego.go:46-213) on
     // 64-bit limbs - two interleaved carry chains per row (A for x*y_i, C for m*q) and no extra top word, which the
     // spare top bit of every modulus in scope allows (field_config.go:200-206). 7-29 % faster than the generic CIOS
     // with a (M+1)-word accumulator it replaces (4 / 6 / 12 limbs), limb-for-limb the same results.
     {
-        constexpr int M = N / 2;
+        constexpr int M = P::N / 2;
         uint64_t a[M], b[M], q[M], t64[M];
         for (int i = 0; i < M; ++i) {
             a[i] = (uint64_t)x.l[2 * i] | ((uint64_t)x.l[2 * i + 1] << 32);
@@ -245,32 +277,7 @@ GMSM_MUL_HD Fp<P> fp_mul(const Fp<P> x, const Fp<P> y) {
         return z;
     }
 #endif
-    uint32_t t[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) t[i] = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const uint32_t yi = y.l[i];
-        uint64_t a = (uint64_t)x.l[0] * yi + t[0];
-        uint32_t A = (uint32_t)(a >> 32);
-        const uint32_t m = (uint32_t)a * P::QINV;
-        uint64_t c = (uint64_t)m * P::Q[0] + (uint32_t)a;
-        uint32_t C = (uint32_t)(c >> 32);
-#pragma unroll
-        for (int j = 1; j < N; ++j) {
-            a = (uint64_t)x.l[j] * yi + t[j] + A;
-            A = (uint32_t)(a >> 32);
-            c = (uint64_t)m * P::Q[j] + (uint32_t)a + C;
-            C = (uint32_t)(c >> 32);
-            t[j - 1] = (uint32_t)c;
-        }
-        t[N - 1] = A + C;  // no-carry condition: cannot overflow
-    }
-    Fp<P> z;
-#pragma unroll
-    for (int i = 0; i < N; ++i) z.l[i] = t[i];
-    fp_reduce_once(z);
-    return z;
+    return fp_mul_inline(x, y);
 }
 
 template <class P>

@@ -24,6 +24,7 @@
 #include "gmsm_scale.h"
 #include "gmsm_ratio.h"
 #include "gmsm_iop_poly.h"
+#include "gmsm_iop_expr.h"
 
 namespace gmsm {
 

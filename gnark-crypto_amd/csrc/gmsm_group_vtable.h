@@ -712,6 +712,49 @@ struct VTableOf {
         HIP_TRY(hipStreamSynchronize(ws.stream));
         return GMSM_OK;
     }
+    // ---- iop.Evaluate of a straight-line program (gmsm_iop_expr.h); in the G1 tables only. ws.poly holds the result of a
+    // host-output call, then the call's small tables in one piece: the constants, the input descriptors, the program.
+    using IE = IopExprField<typename G::FrP>;
+    static int iop_expr(Context &ctx, FftDomain *d, const uint32_t *prog, size_t prog_len, unsigned nregs, const uint64_t *consts, size_t n_consts,
+                        const uint64_t *const *polys, const void *const *d_polys, size_t m, size_t len, const size_t *offsets,
+                        const uint32_t *layouts, int out_layout, hipStream_t caller, uint64_t *out, void *d_out) {
+        GMSM_LEASE_OR_FAIL(lease, ctx);
+        Workspace &ws = *lease.w;
+        int rc;
+        if ((d_polys || d_out) && (rc = order_after(ws, caller))) return rc;  // inputs produced there; it may still use d_out
+        const size_t desc_at = n_consts * sizeof(Fr), prog_at = desc_at + m * sizeof(ExprInput), tab_bytes = prog_at + prog_len * sizeof(uint32_t);
+        const size_t res_bytes = out ? len * sizeof(Fr) : 0;
+        if ((rc = ws.poly.ensure(res_bytes + tab_bytes))) return rc;
+        if (polys && (rc = ws.h2d_scalars.ensure(m * len * sizeof(Fr)))) return rc;
+        unsigned char *dtab = (unsigned char *)ws.poly.ptr + res_bytes;
+        Fr *res = out ? (Fr *)ws.poly.ptr : (Fr *)d_out;
+        std::vector<unsigned char> tab(tab_bytes);
+        if (n_consts) memcpy(tab.data(), consts, n_consts * sizeof(Fr));
+        for (size_t j = 0; j < m; ++j) {
+            ExprInput in;
+            in.ptr = polys ? (const void *)((const Fr *)ws.h2d_scalars.ptr + j * len) : d_polys[j];
+            in.offset = offsets[j], in.rev = layouts[j] == IOP_BIT_REVERSE ? 1u : 0u, in.pad = 0;
+            memcpy(tab.data() + desc_at + j * sizeof(ExprInput), &in, sizeof in);
+        }
+        memcpy(tab.data() + prog_at, prog, prog_len * sizeof(uint32_t));
+        DrainOnExit drain{ws.stream};
+        if (polys)
+            for (size_t j = 0; j < m; ++j)
+                HIP_TRY(hipMemcpyAsync((Fr *)ws.h2d_scalars.ptr + j * len, polys[j], len * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
+        HIP_TRY(hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, ws.stream));
+        ratio_settle_events(ws);
+        StageTimer timer(ws, true);
+        timer.mark(T_DECOMPOSE, ws.stream);
+        const Fr *tw = d && len > 1 ? (const Fr *)d->twiddles_lz.ptr : nullptr;  // built with the domain, read-only since
+        if ((rc = IE::run(ws.stream, (const uint32_t *)(dtab + prog_at), prog_len, nregs, (const Fr *)dtab, (const ExprInput *)(dtab + desc_at), tw, len,
+                          out_layout == (int)IOP_BIT_REVERSE, res)))
+            return rc;
+        for (int ev = T_HIST; ev <= T_END; ++ev) timer.mark(ev, ws.stream);  // the kernel's time goes to slot 0, nothing to the others
+        if (out) HIP_TRY(hipMemcpyAsync(out, res, len * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        if (timer.level == 1) StageTimer::collect(ws);
+        return GMSM_OK;
+    }
     static const GroupVTable *get() {
         // Filled by name: several members have the same type (decode_raw / decode_compressed, fold / jac_to_affine), so a
         // positional list with two of them swapped would compile.
@@ -737,6 +780,7 @@ struct VTableOf {
             GMSM_VT(batch_scale), GMSM_VT(linear_combinations);
             if constexpr (IS_G1) GMSM_VT(fr_batch_invert), GMSM_VT(ratio_copy), GMSM_VT(ratio_shuffled);
             if constexpr (IS_G1) GMSM_VT(iop_to_basis), GMSM_VT(iop_evaluate), GMSM_VT(iop_quotient);
+            if constexpr (IS_G1) GMSM_VT(iop_expr);
 #undef GMSM_VT
             return v;
         }();

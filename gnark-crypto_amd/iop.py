@@ -25,8 +25,16 @@ gmsm_iop_divide_by_x_minus_one:
     y = p.Evaluate(x)                                                 # :104-132; 0 for x in the domain of a Lagrange basis
     q = DivideByXMinusOne(h, (small, big))                            # quotient.go:21-53: Canonical / Regular
 
-with to_basis_device, evaluate_device and divide_by_x_minus_one_device over raw device pointers. iop.Evaluate(f Expression,
-...) takes an arbitrary function and stays on the host.
+with to_basis_device, evaluate_device and divide_by_x_minus_one_device over raw device pointers.
+
+iop.Evaluate(f Expression, r, form, x...) (expressions.go:26-73) over gmsm_iop_evaluate_expression. A closure cannot run on
+the device; an expression is a fixed sequence of field operations, so f is TRACED once with symbols into a straight-line
+program (Program), which one kernel interprets, one index per lane:
+
+    h = Evaluate(lambda i, a, b, c: a * a * b + c - a * a * a, None, Form(LagrangeCoset, Regular), pa, pb, pc)
+    z = Evaluate(lambda i, a: a * i.point(), None, form, pa, domain=d)   # i.point() = w^i, the only use of i there is
+
+with evaluate_expression_device over raw device pointers (one per input: resident polynomials are not concatenated).
 """
 import ctypes
 from collections import namedtuple
@@ -363,4 +371,225 @@ def DivideByXMinusOne(a, domains):
                                                       a.shift % (1 << 64), None, _ptr(out), None))
     res = Polynomial(a.curve, out, (Canonical, Regular))
     res.size = a.size
+    return res
+
+
+# ---- iop.Evaluate (expressions.go:26-73) over gmsm_iop_evaluate_expression
+# the opcodes and limits of include/gmsm.h (GMSM_EXPR_*)
+EXPR_INPUT, EXPR_CONST, EXPR_POINT, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = 1, 2, 3, 4, 5, 6, 7
+EXPR_MAX_REGS, EXPR_MAX_INSNS, EXPR_MAX_INPUTS, EXPR_MAX_CONSTS = 16, 4096, 64, 256
+ErrNoInput = "need at lest one input"  # the reference's text, typo included (expressions.go:39)
+
+Code = namedtuple("Code", ["words", "consts", "has_point"])  # uint32 instruction words, (n_consts, fr_limbs) Montgomery limbs
+
+
+class Symbol:
+    """A value of a Program: the result of one instruction. + - * and unary - make new symbols; a Python int or an array of
+    Montgomery limbs on either side becomes a constant."""
+
+    __slots__ = ("program", "id")
+    __array_ufunc__ = None  # numpy leaves `array * symbol` to __rmul__
+
+    def __init__(self, program, id_):
+        self.program, self.id = program, id_
+
+    def _other(self, o):
+        if isinstance(o, Symbol):
+            if o.program is not self.program:
+                raise ValueError("symbols of two programs")
+            return o
+        return self.program.const(o)
+
+    def __add__(self, o):
+        return self.program._emit(EXPR_ADD, self, self._other(o))
+
+    def __radd__(self, o):
+        return self.program._emit(EXPR_ADD, self._other(o), self)
+
+    def __sub__(self, o):
+        return self.program._emit(EXPR_SUB, self, self._other(o))
+
+    def __rsub__(self, o):
+        return self.program._emit(EXPR_SUB, self._other(o), self)
+
+    def __mul__(self, o):
+        return self.program._emit(EXPR_MUL, self, self._other(o))
+
+    def __rmul__(self, o):
+        return self.program._emit(EXPR_MUL, self._other(o), self)
+
+    def __neg__(self):
+        return self.program._emit(EXPR_NEG, self)
+
+
+class IndexSymbol:
+    """The closure's argument i while it is traced: its only operation is point() = w^i, w = fft.Generator(len)."""
+
+    def __init__(self, program):
+        self.program = program
+
+    def point(self):
+        return self.program.point()
+
+
+class Program:
+    """Builder of a straight-line program. input(j), const(value) and point() give symbols, the operators combine them;
+    build(result) emits the instructions that result needs, in the order they were made (evaluation order; an input, constant
+    or point just before its first use), with registers allocated by liveness: a register is free again after the last use of its symbol, so a symbol used twice is computed once
+    and a chain of products needs two registers. More than 16 live registers raise ValueError."""
+
+    def __init__(self, curve):
+        self.curve = _curve(curve)
+        self.nodes = []  # (op, a, b): a, b symbol ids for the arithmetic, an input / constant index for INPUT / CONST
+        self.consts, self._const_ids, self._input_ids, self._point = [], {}, {}, None
+
+    def _node(self, op, a=0, b=0):
+        self.nodes.append((op, a, b))
+        return Symbol(self, len(self.nodes) - 1)
+
+    def _emit(self, op, a, b=None):
+        return self._node(op, a.id, a.id if b is None else b.id)
+
+    def input(self, j):
+        j = int(j)
+        if not 0 <= j < EXPR_MAX_INPUTS:
+            raise ValueError("input %d is outside [0, %d)" % (j, EXPR_MAX_INPUTS))
+        if j not in self._input_ids:
+            self._input_ids[j] = self._node(EXPR_INPUT, j)
+        return self._input_ids[j]
+
+    def const(self, value):
+        """A Python int is a true value (reduced mod r); anything else is one element in Montgomery limbs."""
+        c = self.curve
+        if isinstance(value, (int, np.integer)):
+            m = int(value) % c.r * c.fr_R % c.r
+            limbs = tuple((m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(c.fr_limbs))
+        else:
+            limbs = tuple(int(v) for v in _elem(c, value))
+        if limbs not in self._const_ids:
+            if len(self.consts) == EXPR_MAX_CONSTS:
+                raise ValueError("more than %d constants" % EXPR_MAX_CONSTS)
+            self.consts.append(limbs)
+            self._const_ids[limbs] = self._node(EXPR_CONST, len(self.consts) - 1)
+        return self._const_ids[limbs]
+
+    def point(self):
+        if self._point is None:
+            self._point = self._node(EXPR_POINT)
+        return self._point
+
+    def index(self):
+        return IndexSymbol(self)
+
+    def build(self, result):
+        if not isinstance(result, Symbol):
+            result = self.const(result)
+        if result.program is not self:
+            raise ValueError("the result is a symbol of another program")
+        arith = (EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG)
+        operands = lambda n: () if n[0] not in arith else (n[1],) if n[0] == EXPR_NEG else (n[1], n[2])
+        needed, stack = set(), [result.id]
+        while stack:
+            k = stack.pop()
+            if k not in needed:
+                needed.add(k)
+                stack.extend(operands(self.nodes[k]))
+        # creation order is evaluation order: operands exist before their users. A leaf (INPUT, CONST, POINT) is emitted just
+        # before its first user, not where it was made: the m inputs of a traced function are not all live from the start
+        order, placed = [], set()
+        for k in sorted(needed):
+            if self.nodes[k][0] in arith:
+                for o in operands(self.nodes[k]):
+                    if self.nodes[o][0] not in arith and o not in placed:
+                        placed.add(o)
+                        order.append(o)
+                order.append(k)
+        if not order:
+            order = [result.id]  # the result is a leaf
+        if len(order) > EXPR_MAX_INSNS:
+            raise ValueError("the program has %d instructions, more than %d" % (len(order), EXPR_MAX_INSNS))
+        last_use = {}
+        for k in order:
+            for o in operands(self.nodes[k]):
+                last_use[o] = k
+        free, reg, words, used_consts, const_at = list(range(EXPR_MAX_REGS - 1, -1, -1)), {}, [], [], {}
+        for k in order:
+            op, a, b = self.nodes[k]
+            ops = operands(self.nodes[k])
+            ra, rb = (reg[ops[0]] if ops else a), (reg[ops[1]] if len(ops) > 1 else 0)
+            if op == EXPR_CONST:  # only the constants the result needs travel
+                if a not in const_at:
+                    const_at[a] = len(used_consts)
+                    used_consts.append(self.consts[a])
+                ra = const_at[a]
+            for o in set(ops):  # the destination may be an operand's register: the lane reads both before it writes
+                if last_use[o] == k:
+                    free.append(reg.pop(o))
+            if not free:
+                raise ValueError("more than %d registers are live at instruction %d" % (EXPR_MAX_REGS, len(words)))
+            free.sort(reverse=True)
+            reg[k] = free.pop()  # the lowest free register: the kernel's register file is sized by the highest one used
+            words.append(op | reg[k] << 8 | ra << 16 | rb << 24)
+        consts = np.array(used_consts, dtype=np.uint64).reshape(-1, self.curve.fr_limbs)
+        return Code(np.array(words, dtype=np.uint32), consts, any(self.nodes[k][0] == EXPR_POINT for k in order))
+
+
+def trace(curve, f, m):
+    """f(i, x_0, .., x_(m-1)) called ONCE with symbols: the Code of its result."""
+    p = Program(curve)
+    return p.build(f(p.index(), *[p.input(j) for j in range(m)]))
+
+
+def _expression_call(c, code, domain, polys, d_polys, m, length, sizes, shifts, layouts, out_layout, stream, out, d_out):
+    words = np.ascontiguousarray(code[0], dtype=np.uint32).reshape(-1)
+    consts = np.ascontiguousarray(code[1], dtype=np.uint64).reshape(-1, c.fr_limbs)
+    sz = np.ascontiguousarray([int(v) for v in sizes], dtype=np.uintp)
+    sh = np.ascontiguousarray([int(v) for v in shifts], dtype=np.int64)
+    lay = _layouts(layouts)
+    if not (len(sz) == len(sh) == len(lay) == m):
+        raise ValueError("sizes, shifts and layouts must have one entry per input")
+    ptrs = None if m == 0 else (ctypes.c_void_p * m)(*[int(v) for v in (polys if polys is not None else d_polys)])
+    _check(_lib.load().gmsm_iop_evaluate_expression(
+        _gid(c), domain.handle if domain is not None else 0, words.ctypes.data_as(_u32p), len(words), _ptr(consts) if len(consts) else None,
+        len(consts), ptrs if polys is not None else None, ptrs if polys is None else None, m, int(length),
+        sz.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), sh.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), lay.ctypes.data_as(_u32p),
+        int(out_layout), stream or None, out, d_out))
+
+
+def evaluate_expression_device(curve, program, d_polys, length, sizes, shifts, layouts, out_layout, d_out, domain=None, stream=0):
+    """The program (a Code, or its (words, consts)) over the m = len(d_polys) polynomials of `length` elements at the device
+    pointers d_polys, produced on `stream`, into d_out - which may be one of them when layout and offset allow (include/gmsm.h).
+    domain: the fft.Domain of cardinality `length`, needed by a program with point()."""
+    _expression_call(_curve(curve), program, domain, None, list(d_polys), len(d_polys), length, sizes, shifts, layouts, out_layout, stream, None,
+                     d_out)
+
+
+def Evaluate(f, r, form, *x, domain=None):
+    """iop.Evaluate (expressions.go:26-73): f(i, x_0, .., x_(m-1)), an ordinary callable over + - * and unary -, applied to
+    the m polynomials index by index on the device; i.point() is w^i. r: None, or the array the result is written to (it may
+    be the coefficients of an input of the result's layout and shift 0). The result has x[0]'s size and shift 0."""
+    if not x:
+        raise ValueError(ErrNoInput)
+    c = x[0].curve
+    n = x[0].coefficients.shape[0]
+    for p in x[1:]:
+        if p.coefficients.shape[0] != n:
+            raise ValueError(ErrInconsistentSize)
+    if r is None:
+        r = np.zeros((n, c.fr_limbs), dtype=np.uint64)
+    elif not (isinstance(r, np.ndarray) and r.dtype == np.uint64 and r.flags.c_contiguous and r.size == n * c.fr_limbs):
+        raise ValueError(ErrInconsistentSize)
+    code = trace(c, f, len(x))
+    own = None
+    if code.has_point and domain is None and n:
+        domain = own = fft.NewDomain(c, n)  # refused there when n is no power of two within the field's 2-adicity
+    try:
+        if n:
+            _expression_call(c, code, domain if code.has_point else None, [p.coefficients.ctypes.data for p in x], None, len(x), n,
+                             [p.size for p in x], [p.shift for p in x], [p.Layout for p in x], form[1], 0, _ptr(r), None)
+    finally:
+        if own is not None:
+            own.release()
+    res = Polynomial(c, r, form)
+    res.size, res.shift = x[0].size, 0
     return res

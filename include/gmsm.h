@@ -503,6 +503,53 @@ int gmsm_iop_evaluate(int group, const uint64_t *polys, const void *d_polys, siz
 int gmsm_iop_divide_by_x_minus_one(uint64_t domain_small, uint64_t domain_big, const uint64_t *a, const void *d_a,
                                    int basis, int layout, uint64_t shift, void *hip_stream, uint64_t *out, void *d_out);
 
+/* ---- iop.Evaluate (ecc/<curve>/fr/iop/expressions.go:26-73) on the device (gmsm_iop_expr.h): a multivariate expression
+ *      applied index by index to m polynomials of len elements each - the constraint numerator on the big coset, between
+ *      gmsm_iop_to_basis and gmsm_iop_divide_by_x_minus_one, without a trip to the host. A Go closure cannot run on a GPU;
+ *      an expression of this kind is a fixed sequence of field additions, subtractions and products, the same for every
+ *      index, so the device form is a small straight-line PROGRAM, validated on the host and interpreted by one kernel, one
+ *      index per lane.
+ *   The program: prog_len words of uint32_t, one instruction per word: op | dst << 8 | a << 16 | b << 24. A lane owns the
+ *      registers 0 .. GMSM_EXPR_MAX_REGS - 1, each one canonical Montgomery fr.Element. At index i:
+ *        GMSM_EXPR_INPUT   dst <- x[a].GetCoeff(i)          GMSM_EXPR_CONST   dst <- consts[a] (n_consts elements, host)
+ *        GMSM_EXPR_POINT   dst <- w^i, w = fft.Generator(len): the closure's argument i, which gnark's numerators use only
+ *                          to index the domain's twiddles (any other function of i: pass it as one more input polynomial)
+ *        GMSM_EXPR_ADD / _SUB / _MUL   dst <- reg[a] (+, -, x) reg[b]          GMSM_EXPR_NEG   dst <- -reg[a]
+ *      The value of the expression is the dst of the last instruction. At most GMSM_EXPR_MAX_INSNS instructions,
+ *      GMSM_EXPR_MAX_INPUTS inputs, GMSM_EXPR_MAX_CONSTS constants. Refused before any device work, each with a text that
+ *      names the instruction index: an unknown opcode, a register >= 16, a read of a register that no earlier instruction
+ *      wrote, an input index >= m or a constant index >= n_consts, POINT without a domain; and an empty or over-long program.
+ *   polys / d_polys: a host array of m pointers (host / device), each to len elements; the inputs are NOT concatenated
+ *      (resident wire polynomials are separate allocations). For i in [0, len), as GetCoeff does (polynomial.go:151-163):
+ *        rho_j = len / sizes[j] (integer division), x_j(i) = element (i + rho_j shifts[j]) mod len of input j, read at that
+ *        index for layouts[j] = 8 (Regular) and at its bit reversal for 16 (BitReverse);
+ *        out[idx(i)] = f(i, x_0(i), ...), idx the identity for out_layout 8, the bit reversal for 16.
+ *      The basis is a label only and stays with the caller. len may be any value >= 1 when every layout is Regular and the
+ *      program has no POINT; else a power of two. With POINT, domain is a gmsm_fft_domain_new handle of the same curve whose
+ *      cardinality is len (0: none). A G2 group id names its curve's scalar field.
+ *   The output may be the same buffer as input j when layouts[j] == out_layout and that input's offset rho_j shifts[j] mod
+ *      len is 0 - the lane that reads a slot is then the one that writes it; any other overlap of the output with an input,
+ *      whole or partial, is refused (host with host, device with device). Inputs are never modified otherwise.
+ *   len == 0 is GMSM_OK and touches nothing. Other errors are GMSM_ERR_ARG with a text: m == 0 ("need at least one input"),
+ *      sizes[j] == 0 or > len, shifts[j] < 0 (the reference panics on the negative index), "layouts[j] = v is no layout", an
+ *      unknown domain handle, a domain of another curve or cardinality, a null required pointer, both or none of a pair.
+ *   With gmsm_set_profiling(1) the kernel's time goes to slot 0 of gmsm_get_stage_times. ---- */
+#define GMSM_EXPR_INPUT 1
+#define GMSM_EXPR_CONST 2
+#define GMSM_EXPR_POINT 3
+#define GMSM_EXPR_ADD 4
+#define GMSM_EXPR_SUB 5
+#define GMSM_EXPR_MUL 6
+#define GMSM_EXPR_NEG 7
+#define GMSM_EXPR_MAX_REGS 16
+#define GMSM_EXPR_MAX_INSNS 4096
+#define GMSM_EXPR_MAX_INPUTS 64
+#define GMSM_EXPR_MAX_CONSTS 256
+int gmsm_iop_evaluate_expression(int group, uint64_t domain, const uint32_t *prog, size_t prog_len, const uint64_t *consts,
+                                 size_t n_consts, const uint64_t *const *polys, const void *const *d_polys, size_t m,
+                                 size_t len, const size_t *sizes, const int64_t *shifts, const uint32_t *layouts,
+                                 int out_layout, void *hip_stream, uint64_t *out, void *d_out);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals
