@@ -12,3 +12,7 @@ from . import shplonk  # noqa: F401  (shplonk mirror: shplonk.BatchOpen, shplonk
 from . import fflonk  # noqa: F401  (fflonk mirror: fflonk.Fold, fflonk.FoldAndCommit, fflonk.BatchOpen, fflonk.OpenW, fflonk.OpenWPrime)
 from . import iop  # noqa: F401  (fr/iop mirror: iop.BuildRatioCopyConstraint, iop.BuildRatioShuffledVectors; fr.BatchInvert as iop.BatchInvert; iop.Polynomial with its basis changes and Evaluate, iop.DivideByXMinusOne, iop.Evaluate over iop.Program)
 from . import mpcsetup  # noqa: F401  (mpcsetup mirror: mpcsetup.UpdateMonomialsG1/G2, mpcsetup.ScaleG1/G2, mpcsetup.BatchScaleG1/G2, mpcsetup.linearCombinationsG1/G2)
+from . import polynomial  # noqa: F401  (fr/polynomial mirror: polynomial.MultiLin with Fold, Evaluate, Eq; polynomial.EvalEq)
+from . import fiatshamir  # noqa: F401  (fiat-shamir mirror: fiatshamir.Transcript, NewTranscript, Bind, ComputeChallenge; host only)
+from . import sumcheck  # noqa: F401  (fr/sumcheck mirror: sumcheck.Prove over a claims object)
+from . import gkr  # noqa: F401  (fr/gkr mirror: gkr.Gate, gkr.Gates, gkr.Wire, gkr.Circuit, gkr.WireAssignment.Complete, gkr.Prove; gkr.Claim is the device handle of one wire's sumcheck claim)

@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "gmsm_to_lagrange_g1", "gmsm_bases_to_lagrange", "gmsm_batch_scale", "gmsm_update_monomials", "gmsm_linear_combinations", "gmsm_shplonk_open_w", "gmsm_shplonk_open_wprime",
     "gmsm_fr_batch_invert", "gmsm_iop_ratio_copy_constraint", "gmsm_iop_ratio_shuffled",
     "gmsm_iop_to_basis", "gmsm_iop_evaluate", "gmsm_iop_divide_by_x_minus_one", "gmsm_iop_evaluate_expression",
+    "gmsm_multilin_fold", "gmsm_multilin_evaluate", "gmsm_multilin_eq",
+    "gmsm_gkr_claim_new", "gmsm_gkr_claim_next", "gmsm_gkr_claim_final", "gmsm_gkr_claim_release",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
     "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_debug_run_layout", "gmsm_debug_fold_planes", "gmsm_debug_plane_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
@@ -224,6 +226,20 @@ def load():
     L.gmsm_iop_divide_by_x_minus_one.argtypes = [ctypes.c_uint64, ctypes.c_uint64, u64p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, vp, u64p, vp]
     L.gmsm_iop_evaluate_expression.restype = ctypes.c_int
     L.gmsm_iop_evaluate_expression.argtypes = [ctypes.c_int, ctypes.c_uint64, u32p, sz, u64p, sz, vp, vp, sz, sz, szp, i64p, u32p, ctypes.c_int, vp, u64p, vp]
+    L.gmsm_multilin_fold.restype = ctypes.c_int
+    L.gmsm_multilin_fold.argtypes = [ctypes.c_int, u64p, vp, sz, u64p, vp]
+    L.gmsm_multilin_evaluate.restype = ctypes.c_int
+    L.gmsm_multilin_evaluate.argtypes = [ctypes.c_int, u64p, vp, sz, u64p, sz, vp, u64p]
+    L.gmsm_multilin_eq.restype = ctypes.c_int
+    L.gmsm_multilin_eq.argtypes = [ctypes.c_int, u64p, sz, u64p, ctypes.c_int, vp, u64p, vp]
+    L.gmsm_gkr_claim_new.restype = ctypes.c_int
+    L.gmsm_gkr_claim_new.argtypes = [ctypes.c_int, u32p, sz, u64p, sz, sz, vp, vp, sz, sz, u64p, sz, u64p, vp, u64p, ctypes.POINTER(ctypes.c_uint64)]
+    L.gmsm_gkr_claim_next.restype = ctypes.c_int
+    L.gmsm_gkr_claim_next.argtypes = [ctypes.c_uint64, u64p, u64p]
+    L.gmsm_gkr_claim_final.restype = ctypes.c_int
+    L.gmsm_gkr_claim_final.argtypes = [ctypes.c_uint64, u64p, u64p]
+    L.gmsm_gkr_claim_release.restype = ctypes.c_int
+    L.gmsm_gkr_claim_release.argtypes = [ctypes.c_uint64]
     L.gmsm_get_stage_launches.restype = ctypes.c_int
     L.gmsm_get_stage_launches.argtypes = [vp, ctypes.c_int]
     ip = ctypes.POINTER(ctypes.c_int)

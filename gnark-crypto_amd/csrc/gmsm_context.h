@@ -163,6 +163,37 @@ struct FftDomain {
     }
 };
 
+// One sumcheck claim of a GKR wire (eqTimesGateEvalSumcheckClaims, ecc/bn254/fr/gkr/gkr.go:143-152) between its rounds: the
+// eq table E and the copies of the gate's m input tables in HBM, the gate program and the round's partial sums. Shared
+// ownership like FftDomain; the Fiat-Shamir step between two rounds is the caller's, which is why this is a handle.
+struct GkrClaim {
+    int group = -1;
+    int device = -1;
+    hipStream_t stream = nullptr;  // the caller's, given to gmsm_gkr_claim_new: every round of the claim runs on it
+    size_t m = 0, degree = 0;
+    size_t stride = 0, len = 0;    // the tables' first and current length (a fold halves len; table t starts at t * stride)
+    unsigned nregs = 0, lanes = 0;
+    uint32_t prog_len = 0;
+    bool finished = false;         // gmsm_gkr_claim_final ran: only release is accepted
+    DeviceBuffer tables;           // (m + 1) x stride elements: E, then the inputs in gate order
+    DeviceBuffer small;            // constants (at 0), program, [workgroup][degree + 1] partial sums, result, points, eq scratch
+    size_t prog_at = 0, partials_at = 0, result_at = 0;  // byte offsets into small
+    std::mutex mu;                 // one round at a time
+    GkrClaim() = default;
+    GkrClaim(const GkrClaim &) = delete;
+    GkrClaim &operator=(const GkrClaim &) = delete;
+    ~GkrClaim() {
+        if (!tables.ptr && !small.ptr) return;
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        if (device >= 0) (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+        tables.release();
+        small.release();
+        (void)hipSetDevice(prev);
+    }
+};
+
 // Everything one in-flight MultiExp needs on the device: scratch buffers, a pinned host buffer for the window totals, a
 // stream of its own (used when the caller gives none) and the stage events. A context owns three of them so that the
 // asynchronous entry points (gmsm_multiexp_bases_submit / _collect) can keep two MultiExp calls in flight: the sort and
@@ -814,6 +845,17 @@ struct GroupVTable {
     int (*iop_expr)(Context &ctx, FftDomain *d, const uint32_t *prog, size_t prog_len, unsigned nregs, const uint64_t *consts, size_t n_consts,
                     const uint64_t *const *polys, const void *const *d_polys, size_t m, size_t len, const size_t *offsets,
                     const uint32_t *layouts, int out_layout, hipStream_t stream, uint64_t *out, void *d_out);
+    // fr/polynomial.MultiLin and one GKR sumcheck claim (gmsm_gkr.h). The engine has validated every argument; a claim comes
+    // with its shape set (GkrClaim: group, device, stream, m, degree, stride = len, nregs, prog_len).
+    int (*multilin_fold)(Context &ctx, uint64_t *a, void *d_a, size_t len, const uint64_t *r, hipStream_t stream);
+    int (*multilin_evaluate)(Context &ctx, const uint64_t *m, const void *d_m, size_t len, const uint64_t *coords, size_t ncoords,
+                             hipStream_t stream, uint64_t *out_value);
+    int (*multilin_eq)(Context &ctx, const uint64_t *q, unsigned n, const uint64_t *scale, int accumulate, hipStream_t stream, uint64_t *out,
+                       void *d_out);
+    int (*gkr_new)(Context &ctx, GkrClaim *claim, const uint32_t *prog, const uint64_t *consts, size_t n_consts, const uint64_t *const *tables,
+                   const void *const *d_tables, const uint64_t *points, size_t k, const uint64_t *comb, uint64_t *out_gj);
+    int (*gkr_next)(GkrClaim *claim, const uint64_t *r, uint64_t *out_gj);
+    int (*gkr_final)(GkrClaim *claim, const uint64_t *r, uint64_t *out_evals);
     unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 

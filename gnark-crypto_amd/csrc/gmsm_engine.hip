@@ -1925,6 +1925,162 @@ GMSM_EXPORT int gmsm_iop_evaluate_expression(int group, uint64_t domain, const u
                         out_layout, (hipStream_t)hip_stream, out, d_out);
 }
 
+// ------------------------------------------------------------------ fr/polynomial.MultiLin and one GKR sumcheck claim (gmsm_gkr.h)
+using GkrRef = std::shared_ptr<GkrClaim>;
+static HandleTable<GkrClaim> g_gkr;
+
+// len = 2^*n, or the refusal
+static int multilin_len(const char *E, size_t len, size_t scalar_bytes, unsigned *n) {
+    if (len == 0 || (len & (len - 1)))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": len = " + std::to_string(len) + " is not a power of two (a MultiLin has 2^n elements)");
+    if (len > ((size_t)1 << 62) / scalar_bytes) return fail(GMSM_ERR_ARG, std::string(E) + ": len does not fit");
+    for (*n = 0; ((size_t)1 << *n) < len; ++*n) {
+    }
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_multilin_fold(int group, uint64_t *a, void *d_a, size_t len, const uint64_t *r, void *hip_stream) {
+    const GroupVTable *vt = fr_vtable(group);
+    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    const char *E = "gmsm_multilin_fold";
+    unsigned n;
+    int rc = multilin_len(E, len, vt->scalar_bytes, &n);
+    if (rc) return rc;
+    if (len == 1) return fail(GMSM_ERR_ARG, std::string(E) + ": len == 1: nothing to fold");
+    if (!r) return fail(GMSM_ERR_ARG, std::string(E) + ": r is null");
+    if ((rc = ratio_pair(E, "a", "d_a", a, d_a))) return rc;
+    Context *ctx;
+    if ((rc = enter_owner(d_a, &ctx)) || (rc = check_device_vector(E, "d_a", d_a, ctx->device))) return rc;
+    return vt->multilin_fold(*ctx, a, d_a, len, r, (hipStream_t)hip_stream);
+}
+
+GMSM_EXPORT int gmsm_multilin_evaluate(int group, const uint64_t *m, const void *d_m, size_t len, const uint64_t *coords, size_t ncoords,
+                                       void *hip_stream, uint64_t *out_value) {
+    const GroupVTable *vt = fr_vtable(group);
+    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    const char *E = "gmsm_multilin_evaluate";
+    unsigned n;
+    int rc = multilin_len(E, len, vt->scalar_bytes, &n);
+    if (rc) return rc;
+    if (ncoords > n)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": ncoords = " + std::to_string(ncoords) + " is more than log2 len = " + std::to_string(n));
+    if (ncoords && !coords) return fail(GMSM_ERR_ARG, std::string(E) + ": coords is null");
+    if (!out_value) return fail(GMSM_ERR_ARG, std::string(E) + ": out_value is null");
+    if ((rc = ratio_pair(E, "m", "d_m", m, d_m))) return rc;
+    Context *ctx;
+    if ((rc = enter_owner(d_m, &ctx)) || (rc = check_device_vector(E, "d_m", d_m, ctx->device))) return rc;
+    return vt->multilin_evaluate(*ctx, m, d_m, len, coords, ncoords, (hipStream_t)hip_stream, out_value);
+}
+
+GMSM_EXPORT int gmsm_multilin_eq(int group, const uint64_t *q, size_t n, const uint64_t *scale, int accumulate, void *hip_stream, uint64_t *out,
+                                 void *d_out) {
+    const GroupVTable *vt = fr_vtable(group);
+    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    const char *E = "gmsm_multilin_eq";
+    if (n >= 8 * sizeof(size_t) || ((size_t)1 << n) > ((size_t)1 << 62) / vt->scalar_bytes)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": n = " + std::to_string(n) + ": 2^n elements are beyond what size_t indexes");
+    if (n && !q) return fail(GMSM_ERR_ARG, std::string(E) + ": q is null");
+    if (!scale) return fail(GMSM_ERR_ARG, std::string(E) + ": scale is null");
+    int rc = ratio_pair(E, "out", "d_out", out, d_out);
+    if (rc) return rc;
+    if (out && n) {
+        const uintptr_t o = (uintptr_t)out, ob = ((size_t)1 << n) * vt->scalar_bytes, p = (uintptr_t)q, pb = n * vt->scalar_bytes;
+        if (o < p + pb && p < o + ob) return fail(GMSM_ERR_ARG, std::string(E) + ": out overlaps q");
+    }
+    Context *ctx;
+    if ((rc = enter_owner(d_out, &ctx)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
+    return vt->multilin_eq(*ctx, q, (unsigned)n, scale, accumulate, (hipStream_t)hip_stream, out, d_out);
+}
+
+GMSM_EXPORT int gmsm_gkr_claim_new(int group, const uint32_t *prog, size_t prog_len, const uint64_t *consts, size_t n_consts, size_t degree,
+                                   const uint64_t *const *tables, const void *const *d_tables, size_t m, size_t len, const uint64_t *points, size_t k,
+                                   const uint64_t *comb, void *hip_stream, uint64_t *out_gj, uint64_t *out_handle) {
+    const GroupVTable *vt = fr_vtable(group);
+    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    const char *E = "gmsm_gkr_claim_new";
+    unsigned n;
+    int rc = multilin_len(E, len, vt->scalar_bytes, &n);
+    if (rc) return rc;
+    if (len == 1) return fail(GMSM_ERR_ARG, std::string(E) + ": len == 1: a sumcheck needs at least one variable");
+    if (m == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": need at least one input (m == 0)");
+    if (m > GMSM_GKR_MAX_INPUTS) return fail(GMSM_ERR_ARG, std::string(E) + ": " + std::to_string(m) + " inputs, more than " + std::to_string(GMSM_GKR_MAX_INPUTS));
+    if (degree == 0 || degree > GMSM_GKR_MAX_DEGREE)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": degree = " + std::to_string(degree) + " is outside [1, " + std::to_string(GMSM_GKR_MAX_DEGREE) + "]");
+    if (k == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": need at least one evaluation point (k == 0)");
+    if (k >= 2 && !comb) return fail(GMSM_ERR_ARG, std::string(E) + ": comb is null with k >= 2");
+    if (n_consts > GMSM_EXPR_MAX_CONSTS)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": " + std::to_string(n_consts) + " constants, more than " + std::to_string(GMSM_EXPR_MAX_CONSTS));
+    if (!prog) return fail(GMSM_ERR_ARG, std::string(E) + ": prog is null");
+    if (n_consts && !consts) return fail(GMSM_ERR_ARG, std::string(E) + ": consts is null");
+    if (!points) return fail(GMSM_ERR_ARG, std::string(E) + ": points is null");
+    if (!out_gj || !out_handle) return fail(GMSM_ERR_ARG, std::string(E) + ": out_gj and out_handle must not be null");
+    if ((rc = ratio_pair(E, "tables", "d_tables", tables, d_tables))) return rc;
+    const void *const *in = tables ? (const void *const *)tables : d_tables;
+    for (size_t j = 0; j < m; ++j)
+        if (!in[j]) return fail(GMSM_ERR_ARG, std::string(E) + ": " + (tables ? "tables[" : "d_tables[") + std::to_string(j) + "] is null");
+    unsigned nregs = 0;
+    bool has_point = false;
+    if ((rc = expr_validate(E, prog, prog_len, m, n_consts, false, &nregs, &has_point))) return rc;  // POINT: a gate has no index
+    if (len > ((size_t)1 << 62) / ((m + 1) * vt->scalar_bytes) || k > ((size_t)1 << 40))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": (m + 1) * len or k does not fit");
+    Context *ctx;
+    if ((rc = enter_owner(d_tables ? d_tables[0] : nullptr, &ctx))) return rc;
+    if (d_tables)
+        for (size_t j = 0; j < m; ++j)
+            if ((rc = check_device_vector(E, ("d_tables[" + std::to_string(j) + "]").c_str(), d_tables[j], ctx->device))) return rc;
+    GkrRef c = std::make_shared<GkrClaim>();
+    c->group = group & ~1, c->device = ctx->device, c->stream = (hipStream_t)hip_stream;
+    c->m = m, c->degree = degree, c->stride = c->len = len, c->nregs = nregs, c->prog_len = (uint32_t)prog_len;
+    if ((rc = vt->gkr_new(*ctx, c.get(), prog, consts, n_consts, tables, d_tables, points, k, comb, out_gj))) return rc;
+    *out_handle = g_gkr.add(c);
+    return GMSM_OK;
+}
+
+// The claim of a handle, locked for one call; refuses an unknown handle and a finished claim
+static int gkr_claim(const char *E, uint64_t handle, const void *r, const void *out, GkrRef *c, const GroupVTable **vt) {
+    if (!(*c = g_gkr.get(handle))) return fail(GMSM_ERR_ARG, "unknown gkr claim handle");
+    if (!r || !out) return fail(GMSM_ERR_ARG, std::string(E) + ": r and the output must not be null");
+    *vt = fr_vtable((*c)->group);
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_gkr_claim_next(uint64_t handle, const uint64_t *r, uint64_t *out_gj) {
+    const char *E = "gmsm_gkr_claim_next";
+    GkrRef c;
+    const GroupVTable *vt;
+    int rc = gkr_claim(E, handle, r, out_gj, &c, &vt);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->finished) return fail(GMSM_ERR_ARG, "the claim is finished");
+    if (c->len == 2)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": the tables have length 2: no variable is left for a round (call gmsm_gkr_claim_final)");
+    Context *ctx;
+    if ((rc = enter_on(c->device, &ctx))) return rc;
+    if ((rc = vt->gkr_next(c.get(), r, out_gj))) c->finished = true;  // a device error: the tables may be half folded
+    return rc;
+}
+
+GMSM_EXPORT int gmsm_gkr_claim_final(uint64_t handle, const uint64_t *r, uint64_t *out_evals) {
+    const char *E = "gmsm_gkr_claim_final";
+    GkrRef c;
+    const GroupVTable *vt;
+    int rc = gkr_claim(E, handle, r, out_evals, &c, &vt);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->finished) return fail(GMSM_ERR_ARG, "the claim is finished");
+    if (c->len != 2)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": the tables have length " + std::to_string(c->len) + ", not 2 (call gmsm_gkr_claim_next)");
+    Context *ctx;
+    if ((rc = enter_on(c->device, &ctx))) return rc;
+    c->finished = true;
+    return vt->gkr_final(c.get(), r, out_evals);
+}
+
+GMSM_EXPORT int gmsm_gkr_claim_release(uint64_t handle) {
+    if (!g_gkr.take(handle)) return fail(GMSM_ERR_ARG, "unknown gkr claim handle");  // the tables go with the last reference
+    return GMSM_OK;
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {
@@ -2288,6 +2444,7 @@ GMSM_EXPORT int gmsm_shutdown(void) {
         const auto bases = g_bases.drain();
         const auto sharded = g_sharded.drain();
         const auto ffts = g_fft.drain();
+        const auto claims = g_gkr.drain();
     }
     int prev = 0;
     (void)hipGetDevice(&prev);

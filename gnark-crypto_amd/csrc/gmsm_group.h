@@ -25,6 +25,7 @@
 #include "gmsm_ratio.h"
 #include "gmsm_iop_poly.h"
 #include "gmsm_iop_expr.h"
+#include "gmsm_gkr.h"
 
 namespace gmsm {
 

@@ -755,6 +755,14 @@ struct VTableOf {
         if (timer.level == 1) StageTimer::collect(ws);
         return GMSM_OK;
     }
+    // ---- fr/polynomial.MultiLin and one GKR sumcheck claim (gmsm_gkr.h); in the G1 tables only
+    using GK = GkrField<typename G::FrP>;
+    static constexpr auto multilin_fold = &GK::multilin_fold;
+    static constexpr auto multilin_evaluate = &GK::multilin_evaluate;
+    static constexpr auto multilin_eq = &GK::multilin_eq;
+    static constexpr auto gkr_new = &GK::gkr_new;
+    static constexpr auto gkr_next = &GK::gkr_next;
+    static constexpr auto gkr_final = &GK::gkr_final;
     static const GroupVTable *get() {
         // Filled by name: several members have the same type (decode_raw / decode_compressed, fold / jac_to_affine), so a
         // positional list with two of them swapped would compile.
@@ -781,6 +789,9 @@ struct VTableOf {
             if constexpr (IS_G1) GMSM_VT(fr_batch_invert), GMSM_VT(ratio_copy), GMSM_VT(ratio_shuffled);
             if constexpr (IS_G1) GMSM_VT(iop_to_basis), GMSM_VT(iop_evaluate), GMSM_VT(iop_quotient);
             if constexpr (IS_G1) GMSM_VT(iop_expr);
+            if constexpr (IS_G1)
+                v.multilin_fold = multilin_fold, v.multilin_evaluate = multilin_evaluate, v.multilin_eq = multilin_eq, v.gkr_new = gkr_new,
+                v.gkr_next = gkr_next, v.gkr_final = gkr_final;
 #undef GMSM_VT
             return v;
         }();

@@ -550,6 +550,62 @@ int gmsm_iop_evaluate_expression(int group, uint64_t domain, const uint32_t *pro
                                  size_t len, const size_t *sizes, const int64_t *shifts, const uint32_t *layouts,
                                  int out_layout, void *hip_stream, uint64_t *out, void *d_out);
 
+/* ---- fr/polynomial.MultiLin (ecc/<curve>/fr/polynomial/multilin.go) and the sumcheck claim of one GKR wire
+ *      (eqTimesGateEvalSumcheckClaims, ecc/<curve>/fr/gkr/gkr.go:143-348) on the device (gmsm_gkr.h): the prover side of
+ *      the reference's second proving stack, whose loops run over the 2^n instances of a circuit. Conventions are those of
+ *      the iop entries: Montgomery fr.Element limbs; a G2 group id names its curve's scalar field; exactly one of each host /
+ *      device pointer pair; device pointers 16-byte aligned and produced on hip_stream; the call returns when its result is
+ *      complete; every error the host can decide is GMSM_ERR_ARG with a text, before any device work, and nothing is
+ *      written. Table lengths are powers of two, len = 2^n, and variable X_1 is the most significant bit of an index
+ *      (multilin.go:14-17). Results are the reference's bit for bit: each is a uniquely determined canonical element.
+ *   gmsm_multilin_fold: (*MultiLin).Fold, in place: a[i] <- a[i] + r (a[i + len/2] - a[i]) for i < len / 2; the elements
+ *      [len/2, len) are not written (the reference leaves them as they were). len == 1 is refused: nothing to fold.
+ *   gmsm_multilin_evaluate: (MultiLin).Evaluate: ncoords folds of a scratch copy, one after the other without a host wait,
+ *      then element 0 to out_value (host). m is never modified. ncoords in [0, log2 len]; 0 returns m[0]. coords: host.
+ *   gmsm_multilin_eq: (*MultiLin).Eq with m[0] = scale, and eqAcc (gkr.go:190-226) when accumulate != 0: for h < 2^n,
+ *      v(h) = scale prod_{i<n} (bit_{n-1-i}(h) ? q[i] : 1 - q[i]); out[h] <- v(h), or out[h] <- out[h] + v(h). n == 0 gives
+ *      out[0] = scale (or adds it). q, scale: host. Refused: n beyond what size_t indexes, a host output that overlaps q.
+ *   A claim is a HANDLE that owns its tables in HBM between the rounds, because the Fiat-Shamir step between two rounds is the
+ *      caller's. gmsm_shutdown releases every claim; gmsm_trim leaves them alone (their memory is in use).
+ *   gmsm_gkr_claim_new: tables / d_tables is a host array of m pointers (host / device), each to len elements: the gate's
+ *      input assignments (inputPreprocessors), in gate order; the same pointer may appear more than once. They are COPIED
+ *      (gkr.go:397-403: folding destroys them); the caller's arrays are never modified. points (host): k >= 1 evaluation
+ *      points of n = log2 len elements each; the claim's eq table is E = sum_{j<k} comb^j eq(points[j], .) (Combine,
+ *      gkr.go:154-187); comb (host) is read only when k >= 2. prog is a GMSM_EXPR_* program (above) over the gate's inputs:
+ *      INPUT a is gate input a < m, POINT is refused (a gate has no index), the value is the dst of the last instruction; it
+ *      passes the same checks, with the same texts. degree is Gate.Degree(): an upper bound of the true degree, not checked
+ *      against the program. out_gj (host) receives the first round polynomial, degree + 1 elements, on hip_stream, on
+ *      which every later round of the claim runs too.
+ *   The round polynomial (computeGJ): with the tables T_0 = E, T_1 .. T_m of current length L and half = L / 2,
+ *      f_{t,d}(i) = T_t[i + half] + d (T_t[i + half] - T_t[i]) for d = 0 .. degree, and
+ *      out_gj[d] = sum_{i<half} f_{0,d}(i) G(f_{1,d}(i), .., f_{m,d}(i)): g(1) .. g(degree + 1); g(0) is never sent.
+ *   gmsm_gkr_claim_next: Next (gkr.go:296-317): every table is folded by r, then the round polynomial of the folded
+ *      tables, in one pass. Refused when the tables have length 2: no variable is left, call gmsm_gkr_claim_final.
+ *   gmsm_gkr_claim_final: the fold of ProveFinalEval (gkr.go:338): the m input tables, which must have length 2, are folded
+ *      by r; out_evals (host) receives element 0 of each, m elements in input order (which of them become claims - the first
+ *      occurrence of each distinct input wire - is the caller's business). Afterwards the handle accepts only release.
+ *   Errors (GMSM_ERR_ARG, with a text): an unknown group; len zero or no power of two; len == 1 for a claim (the
+ *      reference's sumcheck.Prove indexes an empty slice for zero variables); m == 0 or > GMSM_GKR_MAX_INPUTS; degree == 0 or
+ *      > GMSM_GKR_MAX_DEGREE; k == 0; comb null with k >= 2; a null required pointer, both or none of a pair, a null table
+ *      pointer ("tables[j] is null"); every program error; "unknown gkr claim handle"; "the claim is finished";
+ *      next at length 2, final at another length; evaluate with ncoords > log2 len.
+ *   The gate program's register file is in LDS and its operands are reloaded per point, so every valid program fits the
+ *      kernel's budget: no claim is refused for its size. ---- */
+#define GMSM_GKR_MAX_INPUTS 16
+#define GMSM_GKR_MAX_DEGREE 15
+int gmsm_multilin_fold(int group, uint64_t *a, void *d_a, size_t len, const uint64_t *r, void *hip_stream);
+int gmsm_multilin_evaluate(int group, const uint64_t *m, const void *d_m, size_t len, const uint64_t *coords,
+                           size_t ncoords, void *hip_stream, uint64_t *out_value);
+int gmsm_multilin_eq(int group, const uint64_t *q, size_t n, const uint64_t *scale, int accumulate, void *hip_stream,
+                     uint64_t *out, void *d_out);
+int gmsm_gkr_claim_new(int group, const uint32_t *prog, size_t prog_len, const uint64_t *consts, size_t n_consts,
+                       size_t degree, const uint64_t *const *tables, const void *const *d_tables, size_t m, size_t len,
+                       const uint64_t *points, size_t k, const uint64_t *comb, void *hip_stream, uint64_t *out_gj,
+                       uint64_t *out_handle);
+int gmsm_gkr_claim_next(uint64_t handle, const uint64_t *r, uint64_t *out_gj);
+int gmsm_gkr_claim_final(uint64_t handle, const uint64_t *r, uint64_t *out_evals);
+int gmsm_gkr_claim_release(uint64_t handle);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals
