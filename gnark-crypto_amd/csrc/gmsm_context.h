@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <chrono>
 #include <condition_variable>
 #include <map>
@@ -119,7 +120,6 @@ struct ResidentBases {
         (void)hipSetDevice(prev);
     }
 };
-
 
 // One fft.Domain (ecc/bn254/fr/fft/domain.go:24-60) resident on a device: the constants on the host (Montgomery limbs),
 // the twiddle and coset tables in HBM. Shared ownership like ResidentBases.
@@ -515,6 +515,19 @@ static inline int stage_input(Workspace &ws, DeviceBuffer &stage, const void *ho
     return GMSM_OK;
 }
 
+struct DrainOnExit {  // holds a call's pageable staging vectors until its stream has drained, whichever way the call leaves
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// one field element from the ABI's limbs (canonical Montgomery form, as the caller gives it)
+template <class Fr>
+static inline Fr fr_from_limbs(const uint64_t *p) {
+    Fr v;
+    memcpy(&v, p, sizeof v);
+    return v;
+}
+
 // Scratch of a workspace is reused by every call that leases it; calls may run on different streams (the workspace's
 // own, or the caller's for the enqueue-only entry). begin_use orders `stream` behind the last work enqueued on the
 // workspace, end_use publishes the end of this call's work.
@@ -589,7 +602,6 @@ int get_context_for(int device, Context **out);
 // Context of the device that owns the device pointer `p` (the calling thread's device when p is null or unknown to
 // the runtime): the device-pointer entries do not depend on which OS thread the caller happens to run on.
 int get_context_of_pointer(const void *p, Context **out);
-
 
 // ------------------------------------------------------------------ point ingest status (gmsm_ingest.h)
 enum PointStatus : uint32_t {
@@ -756,10 +768,6 @@ struct GroupVTable {
     int (*decode_compressed)(Workspace &ws, const void *d_comp, size_t n, int level, void *d_out, long long *bad_index,
                              uint32_t *status);
     int (*encode_compressed)(Workspace &ws, const void *d_points, size_t n, void *d_comp);
-    // fr/fft over the group's scalar field (gmsm_fft.h)
-    int (*fft_domain_new)(Context &ctx, hipStream_t stream, unsigned log2n, FftDomain *out);
-    int (*fft_run)(hipStream_t stream, FftDomain *d, void *d_a, bool inverse, bool dif, bool coset);
-    int (*fft_bit_reverse)(hipStream_t stream, void *d_a, size_t n);
     // one rank's piece of a MultiExp that the library shards over several devices (Group::shard_piece)
     int (*precompute_tables)(Context &ctx, Workspace &ws, ResidentBases *rb, unsigned c);  // window tables of registered bases
     bool (*tables_serve)(size_t n_registered, size_t n_call);  // call sizes that run through the tables (Group::use_tables)
@@ -773,34 +781,24 @@ struct GroupVTable {
     int (*run_layout)(int num_cus, size_t n, unsigned c, unsigned win_first, unsigned win_stride, bool glv, bool shared, unsigned flags,
                       uint64_t *out);  // gmsm_debug_run_layout
     void (*fold_planes)(const uint64_t *planes, unsigned c, unsigned nwin, unsigned log2L, unsigned nhigh, uint64_t *out_jac);  // gmsm_debug_fold_planes
-    // KZG opening over the group's scalar field (gmsm_poly.h): polynomials are host (`polys`) or device (`d_polys`) fr.Element
-    // vectors, k of them concatenated (lens[i] elements each), never modified
-    int (*poly_eval)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
-                     hipStream_t stream, uint64_t *out_values);
-    int (*poly_div)(Context &ctx, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point, hipStream_t stream,
-                    uint64_t *out_h, void *d_out_h, uint64_t *out_value);
+    // KZG opening (gmsm_poly.h), polynomials as for FieldVTable::poly_eval:
     // H = MultiExp(resident[:maxlen - 1], (sum_i gamma^i f_i) / (X - point)); gamma == nullptr: k == 1, no fold
     int (*kzg_open)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
                     const uint64_t *gamma, hipStream_t stream, uint64_t *out_claimed, uint64_t *out_jac, const ResidentBases *resident);
-    // ToLagrangeG1 (gmsm_group_fft.h) of n = 2^log2n points, log2n <= fr_max_order: the input is host `coeffs`, device
+    // ToLagrangeG1 (gmsm_group_fft.h) of n = 2^log2n points, log2n <= FieldVTable::fr_max_order: the input is host `coeffs`, device
     // `d_coeffs` or the first n bases of `from`; the output goes to host `out_affine`, device `d_out_affine` or a new
     // registration `out_bases`. nullptr for the G2 groups.
     int (*to_lagrange)(Context &ctx, const uint64_t *coeffs, const void *d_coeffs, const ResidentBases *from, unsigned log2n,
                        hipStream_t stream, uint64_t *out_affine, void *d_out_affine, ResidentBases *out_bases);
     // shplonk and fflonk over registered G1 bases (gmsm_fflonk.h, gmsm_shplonk.h): polynomials as for kzg_open, all polynomials
     // of all k packs concatenated, lens[] per polynomial, pack_sizes[] per pack; `points` holds the k sets one after the other
-    // (npoints[i] elements each, host). pack_sizes == null is shplonk: k polynomials, each opened on its own set.
-    //   fflonk_next_divisor: getNextDivisorRMinusOne over the group's scalar field, host only; false when there is none
-    //   open_check: every refusal that depends on the packs and the points (points == null: the packs alone), host only;
-    //               `registered` bases for the size condition of the open entries (check_size)
+    // (npoints[i] elements each, host). pack_sizes == null is shplonk: k polynomials, each opened on its own set. The engine
+    // has run FieldVTable::open_check on the same arguments.
     //   fflonk_fold: Fold of one pack to out (host) / d_out (device) / the workspace (both null), and with `resident` its Commit
     //   open_w: the claimed values (shplonk: out_claimed in the layout of points, out_folded_claimed unused; fflonk: both
     //           sets), w (max_i t_i n_i elements) to out_w (host) or d_out_w (device), W = Commit(w)
     //   open_wprime: W' = Commit((sum_i c_i F_i - sum_i c_i r_i(z) - Z_T(z) w) / (X - z)) from shplonk's claimed values (for
     //                fflonk the folded ones), w from the host or the device. Both nullptr for the G2 groups.
-    bool (*fflonk_next_divisor)(size_t n, size_t *t);
-    int (*open_check)(const char *entry, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
-                      const size_t *npoints, bool check_size, size_t registered);
     int (*fflonk_fold)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t npolys, hipStream_t stream,
                        uint64_t *out, void *d_out, const ResidentBases *resident, uint64_t *out_jac);
     int (*open_w)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, const size_t *pack_sizes, size_t k,
@@ -817,9 +815,31 @@ struct GroupVTable {
     // linearCombinationsG1/G2: the two sums over powers of r with zeros at the segment ends (checked by the caller), Jacobian
     int (*linear_combinations)(Context &ctx, const uint64_t *points, const void *d_points, size_t n, const size_t *ends, size_t n_ends,
                                const uint64_t *r, hipStream_t stream, uint64_t *out_truncated_jac, uint64_t *out_shifted_jac);
-    // fr.BatchInvert and the iop ratio polynomials over the group's scalar field (gmsm_ratio.h); nullptr for the G2 groups (the
-    // engine goes through the pair's G1 table). Vectors on the host or on the device as for poly_div; the m polynomials of
-    // n = the domain's cardinality elements are concatenated, in Lagrange basis, layouts[j] = 8 (Regular) / 16 (BitReverse).
+};
+
+// The function table of one curve's scalar field: everything that is over Fr alone and touches no point type. One per curve,
+// shared by its two groups (gmsm_field_vtable.h; the engine's fr_vtable()).
+struct FieldVTable {
+    size_t scalar_bytes;
+    unsigned fr_bits, fr_max_order;  // fr_max_order: the field's 2-adicity (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
+    // fr/fft (gmsm_fft.h)
+    int (*fft_domain_new)(Context &ctx, hipStream_t stream, unsigned log2n, FftDomain *out);
+    int (*fft_run)(hipStream_t stream, FftDomain *d, void *d_a, bool inverse, bool dif, bool coset);
+    int (*fft_bit_reverse)(hipStream_t stream, void *d_a, size_t n);
+    // KZG's evaluation and quotient (gmsm_poly.h): polynomials are host (`polys`) or device (`d_polys`) fr.Element vectors, k of
+    // them concatenated (lens[i] elements each), never modified
+    int (*poly_eval)(Context &ctx, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k, const uint64_t *point,
+                     hipStream_t stream, uint64_t *out_values);
+    int (*poly_div)(Context &ctx, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point, hipStream_t stream,
+                    uint64_t *out_h, void *d_out_h, uint64_t *out_value);
+    // the host checks of shplonk and fflonk (gmsm_fflonk.h; arguments as for GroupVTable::open_w). fflonk_next_divisor:
+    // getNextDivisorRMinusOne, false when there is none. open_check: every refusal that depends on the packs and the points
+    // (points == null: the packs alone); `registered` bases for the size condition of the open entries (check_size)
+    bool (*fflonk_next_divisor)(size_t n, size_t *t);
+    int (*open_check)(const char *entry, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
+                      const size_t *npoints, bool check_size, size_t registered);
+    // fr.BatchInvert and the iop ratio polynomials (gmsm_ratio.h). Vectors on the host or on the device as for poly_div; the m polynomials
+    // of n = the domain's cardinality elements are concatenated, in Lagrange basis, layouts[j] = 8 (Regular) / 16 (BitReverse).
     int (*fr_batch_invert)(Context &ctx, const uint64_t *a, const void *d_a, size_t n, hipStream_t stream, uint64_t *out, void *d_out);
     int (*ratio_copy)(Context &ctx, FftDomain *d, const uint64_t *entries, const void *d_entries, size_t m, const uint32_t *layouts,
                       const int64_t *perm, const void *d_perm, const uint64_t *beta, const uint64_t *gamma, int basis, int layout,
@@ -827,8 +847,7 @@ struct GroupVTable {
     int (*ratio_shuffled)(Context &ctx, FftDomain *d, const uint64_t *num, const void *d_num, const uint64_t *den, const void *d_den,
                           size_t m, const uint32_t *num_layouts, const uint32_t *den_layouts, const uint64_t *beta, int basis, int layout,
                           hipStream_t stream, uint64_t *out, void *d_out);
-    // iop.Polynomial over the group's scalar field (gmsm_iop_poly.h); nullptr for the G2 groups, as above. The engine has
-    // checked every argument: values of basis / layout, powers of two, the field's 2-adicity, overlaps.
+    // iop.Polynomial (gmsm_iop_poly.h). The engine has checked every argument: basis / layout values, powers of two, 2-adicity, overlaps.
     //   iop_to_basis: in place on a (host) / d_a (device), cardinality elements of which the first len are given
     //   iop_evaluate: k polynomials of len elements, concatenated; shift in 0..5; coset given when basis is LagrangeCoset
     //   iop_quotient: DivideByXMinusOne of the card(big) elements of a; shift already reduced mod card(small)
@@ -856,7 +875,6 @@ struct GroupVTable {
                    const void *const *d_tables, const uint64_t *points, size_t k, const uint64_t *comb, uint64_t *out_gj);
     int (*gkr_next)(GkrClaim *claim, const uint64_t *r, uint64_t *out_gj);
     int (*gkr_final)(GkrClaim *claim, const uint64_t *r, uint64_t *out_evals);
-    unsigned fr_max_order;  // 2-adicity of the scalar field (FrP::MAX_ORDER): fr.Generator(n) exists for n <= 2^fr_max_order
 };
 
 }  // namespace gmsm

@@ -195,14 +195,30 @@ static const GroupVTable *vtable(int group) {
     }
 }
 
+// the scalar field's entries: one table per curve, the same for both of its groups (gmsm_field_vtable.h)
+const FieldVTable *gmsm_field_vtable_bn254();
+const FieldVTable *gmsm_field_vtable_bls12_381();
+const FieldVTable *gmsm_field_vtable_bw6_761();
+
+static const FieldVTable *fr_vtable(int group) {
+    switch (group >> 1) {  // (a negative id stays negative or turns huge: no curve either way)
+        case GMSM_BN254_G1 >> 1: return gmsm_field_vtable_bn254();
+        case GMSM_BLS12_381_G1 >> 1: return gmsm_field_vtable_bls12_381();
+        case GMSM_BW6_761_G1 >> 1: return gmsm_field_vtable_bw6_761();
+        default: return nullptr;
+    }
+}
+
 }  // namespace gmsm
 
 using namespace gmsm;
 
 #define GMSM_EXPORT __attribute__((visibility("default")))
-#define VT_OR_FAIL(group)                          \
-    const GroupVTable *vt = vtable(group);         \
+#define TABLE_OR_FAIL(Table, lookup, group)        \
+    const Table *vt = lookup(group);               \
     if (!vt) return fail(GMSM_ERR_ARG, "unknown group id")
+#define VT_OR_FAIL(group) TABLE_OR_FAIL(GroupVTable, vtable, group)
+#define FR_OR_FAIL(group) TABLE_OR_FAIL(FieldVTable, fr_vtable, group)  // an entry over the scalar field alone
 
 // ------------------------------------------------------------------ one MultiExp over several devices
 // The reference spreads one MultiExp over the cores of a machine: _innerMsmG1 starts a worker per c-bit window and
@@ -1157,7 +1173,7 @@ using FftRef = std::shared_ptr<FftDomain>;
 static HandleTable<FftDomain> g_fft;
 
 GMSM_EXPORT int gmsm_fft_domain_new(int group, uint64_t m, uint64_t *out_handle) {
-    VT_OR_FAIL(group);
+    FR_OR_FAIL(group);
     if (!out_handle) return fail(GMSM_ERR_ARG, "gmsm_fft_domain_new: out_handle is null");
     unsigned log2n = 0;  // ecc.NextPowerOfTwo(m)
     while (log2n < 63 && ((uint64_t)1 << log2n) < m) ++log2n;
@@ -1199,7 +1215,7 @@ GMSM_EXPORT int gmsm_fft(uint64_t handle, uint64_t *a, void *d_a, size_t n, int 
                          void *hip_stream) {
     FftRef d = g_fft.get(handle);
     if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
-    const GroupVTable *vt = vtable(d->group);
+    const FieldVTable *vt = fr_vtable(d->group);
     if (n != ((size_t)1 << d->log2n)) return fail(GMSM_ERR_LEN, "len(a) must equal the domain's cardinality");
     if ((a == nullptr) == (d_a == nullptr)) return fail(GMSM_ERR_ARG, "gmsm_fft: give exactly one of a (host) / d_a (device)");
     if (decimation != 0 && decimation != 1) return fail(GMSM_ERR_ARG, "gmsm_fft: decimation must be 0 (DIT) or 1 (DIF)");
@@ -1229,7 +1245,7 @@ GMSM_EXPORT int gmsm_fft(uint64_t handle, uint64_t *a, void *d_a, size_t n, int 
 }
 
 GMSM_EXPORT int gmsm_fft_bit_reverse(int group, uint64_t *a, void *d_a, size_t n, void *hip_stream) {
-    VT_OR_FAIL(group);
+    FR_OR_FAIL(group);
     if ((a == nullptr) == (d_a == nullptr) && n) return fail(GMSM_ERR_ARG, "gmsm_fft_bit_reverse: give exactly one of a / d_a");
     if (n == 0) return GMSM_OK;
     Context *ctx;
@@ -1263,7 +1279,7 @@ static int check_device_vector(const char *entry, const char *name, const void *
 
 GMSM_EXPORT int gmsm_poly_eval(int group, const uint64_t *polys, const void *d_polys, const size_t *lens, size_t k,
                                const uint64_t *point, void *hip_stream, uint64_t *out_values) {
-    VT_OR_FAIL(group);
+    FR_OR_FAIL(group);
     if (k == 0) return GMSM_OK;
     if (!lens || !point || !out_values) return fail(GMSM_ERR_ARG, "gmsm_poly_eval: lens, point and out_values must not be null");
     if ((polys == nullptr) == (d_polys == nullptr))
@@ -1280,7 +1296,7 @@ GMSM_EXPORT int gmsm_poly_eval(int group, const uint64_t *polys, const void *d_p
 
 GMSM_EXPORT int gmsm_poly_div_x_minus_a(int group, const uint64_t *poly, const void *d_poly, size_t n, const uint64_t *point,
                                         void *hip_stream, uint64_t *out_h, void *d_out_h, uint64_t *out_value) {
-    VT_OR_FAIL(group);
+    FR_OR_FAIL(group);
     const char *E = "gmsm_poly_div_x_minus_a";
     if (n == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": n == 0 (f(a) of an empty polynomial is undefined)");
     if (!point) return fail(GMSM_ERR_ARG, std::string(E) + ": point is null");
@@ -1342,7 +1358,7 @@ static const char *const ERR_FFLONK_G1 = "fflonk commits and opens over G1 bases
 // The four open entries take shplonk's k polynomials (pack_sizes is no argument of theirs: null from here on) or fflonk's k
 // packs. Their checks, in this order: the counts and arrays (open_nonempty), the entry's own pointers and aliases, then
 // open_check: the polynomials' pointer pair, the handle, G1, every refusal that depends on the polynomials and the points
-// (GroupVTable::open_check: shplonk.go:44-83, fflonk.go:77-141), the size condition last - the reference commits w' over
+// (FieldVTable::open_check: shplonk.go:44-83, fflonk.go:77-141), the size condition last - the reference commits w' over
 // maxSizePolys + sum_i npoints[i] - 1 coefficients, so that many bases must be registered although the device MSMs run over
 // true lengths only (kzg.go:159-162) - all on the host, then the device of the bases.
 static int open_nonempty(const char *E, bool packed, const size_t *lens, const size_t *pack_sizes, size_t k, const uint64_t *points,
@@ -1360,7 +1376,7 @@ static int open_check(const char *E, uint64_t handle, const uint64_t *polys, con
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
     if (!vt->open_w) return fail(GMSM_ERR_ARG, pack_sizes ? ERR_FFLONK_G1 : ERR_SHPLONK_G1);
-    int rc = vt->open_check(E, lens, pack_sizes, k, points, npoints, true, rb->n);
+    int rc = fr_vtable(rb->group)->open_check(E, lens, pack_sizes, k, points, npoints, true, rb->n);
     if (rc) return rc;
     Context *ctx;
     if ((rc = enter_on(rb->device, &ctx))) return rc;  // the bases decide the device
@@ -1412,7 +1428,7 @@ GMSM_EXPORT int gmsm_shplonk_open_wprime(uint64_t handle, const uint64_t *polys,
 // ------------------------------------------------------------------ fflonk Fold, FoldAndCommit, BatchOpen (gmsm_fflonk.h)
 
 GMSM_EXPORT int gmsm_fflonk_next_divisor(int group, size_t n, size_t *out_t) {
-    VT_OR_FAIL(group);
+    FR_OR_FAIL(group);
     const char *E = "gmsm_fflonk_next_divisor";
     if (!out_t) return fail(GMSM_ERR_ARG, std::string(E) + ": out_t is null");
     if (n == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": n == 0");
@@ -1436,7 +1452,7 @@ GMSM_EXPORT int gmsm_fflonk_fold(int group, const uint64_t *polys, const void *d
     if ((polys && polys == out) || (d_polys && d_polys == d_out))
         return fail(GMSM_ERR_ARG, std::string(E) + ": the output aliases the input (inputs are never modified)");
     int rc = fflonk_pack_args(E, polys, d_polys, lens, npolys);
-    if (rc || (rc = vt->open_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
+    if (rc || (rc = fr_vtable(group)->open_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
     Context *ctx;
     if ((rc = enter_owner(d_polys ? d_polys : d_out, &ctx))) return rc;
     if ((rc = check_device_vector(E, "d_polys", d_polys, ctx->device)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
@@ -1455,9 +1471,9 @@ GMSM_EXPORT int gmsm_fflonk_fold_commit(uint64_t handle, const uint64_t *polys, 
     if (!rb) return fail(GMSM_ERR_ARG, "unknown bases handle");
     const GroupVTable *vt = vtable(rb->group);
     if (!vt->open_w) return fail(GMSM_ERR_ARG, ERR_FFLONK_G1);
-    if ((rc = vt->open_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
+    if ((rc = fr_vtable(rb->group)->open_check(E, lens, &npolys, 1, nullptr, nullptr, false, 0))) return rc;
     size_t t = 0, n = 0;
-    vt->fflonk_next_divisor(npolys, &t);
+    fr_vtable(rb->group)->fflonk_next_divisor(npolys, &t);
     for (size_t j = 0; j < npolys; ++j) n = std::max(n, lens[j]);
     if (t * n > rb->n) return fail(GMSM_ERR_ARG, ERR_POLY_SIZE);  // Commit's size check (kzg.go:159-162) over the folded length
     Context *ctx;
@@ -1520,7 +1536,7 @@ static const char *const ERR_G1_ONLY = "ToLagrangeG1 is defined for G1 only";
 static const char *const ERR_ROOT = "m is too big: the required root of unity does not exist";  // as gmsm_fft_domain_new
 
 // the size checks of ToLagrangeG1 and computeTwiddlesInv (fr.Generator): no device needed
-static int lagrange_size(const GroupVTable *vt, size_t n, unsigned *log2n) {
+static int lagrange_size(const FieldVTable *vt, size_t n, unsigned *log2n) {
     if (n == 0 || (n & (n - 1))) return fail(GMSM_ERR_ARG, ERR_POW2);
     unsigned l = 0;
     while (((size_t)1 << l) < n) ++l;
@@ -1535,7 +1551,7 @@ GMSM_EXPORT int gmsm_to_lagrange_g1(int group, const uint64_t *coeffs, const voi
     const char *E = "gmsm_to_lagrange_g1";
     if (!vt->to_lagrange) return fail(GMSM_ERR_ARG, ERR_G1_ONLY);
     unsigned log2n;
-    int rc = lagrange_size(vt, n, &log2n);
+    int rc = lagrange_size(fr_vtable(group), n, &log2n);
     if (rc) return rc;
     if ((coeffs == nullptr) == (d_coeffs == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of coeffs (host) / d_coeffs (device)");
     if ((out_affine == nullptr) == (d_out_affine == nullptr))
@@ -1554,7 +1570,7 @@ GMSM_EXPORT int gmsm_bases_to_lagrange(uint64_t handle, size_t n, uint64_t *out_
     const GroupVTable *vt = vtable(rb->group);
     if (!vt->to_lagrange) return fail(GMSM_ERR_ARG, ERR_G1_ONLY);
     unsigned log2n;
-    int rc = lagrange_size(vt, n, &log2n);
+    int rc = lagrange_size(fr_vtable(rb->group), n, &log2n);
     if (rc) return rc;
     if (n > rb->n) return fail(GMSM_ERR_ARG, "gmsm_bases_to_lagrange: n is larger than the registered bases");
     Context *ctx;
@@ -1621,12 +1637,8 @@ GMSM_EXPORT int gmsm_linear_combinations(int group, const uint64_t *points, cons
 }
 
 // ------------------------------------------------------------------ fr.BatchInvert, iop ratio polynomials (gmsm_ratio.h)
-// the scalar field's entries live in the table of the pair's G1 group (even id)
-static const GroupVTable *fr_vtable(int group) { return vtable(group) ? vtable(group & ~1) : nullptr; }
-
 GMSM_EXPORT int gmsm_fr_batch_invert(int group, const uint64_t *a, const void *d_a, size_t n, void *hip_stream, uint64_t *out, void *d_out) {
-    const GroupVTable *vt = fr_vtable(group);
-    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    FR_OR_FAIL(group);
     const char *E = "gmsm_fr_batch_invert";
     if (n == 0) return GMSM_OK;
     if ((a == nullptr) == (d_a == nullptr)) return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of a (host) / d_a (device)");
@@ -1663,7 +1675,7 @@ static int ratio_pair(const char *E, const char *host, const char *dev, const vo
         return fail(GMSM_ERR_ARG, std::string(E) + ": give exactly one of " + host + " (host) / " + dev + " (device)");
     return GMSM_OK;
 }
-static int ratio_domain(const char *E, uint64_t domain, size_t m, FftRef *d_out_ref, const GroupVTable **vt_out) {
+static int ratio_domain(const char *E, uint64_t domain, size_t m, FftRef *d_out_ref, const FieldVTable **vt_out) {
     FftRef d = g_fft.get(domain);
     if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
     if (m > (((size_t)1 << 62) >> d->log2n)) return fail(GMSM_ERR_ARG, std::string(E) + ": m * n does not fit");
@@ -1686,7 +1698,7 @@ GMSM_EXPORT int gmsm_iop_ratio_copy_constraint(uint64_t domain, const uint64_t *
     if (!beta || !gamma) return fail(GMSM_ERR_ARG, std::string(E) + ": beta and gamma must not be null");
     if ((rc = ratio_pair(E, "entries", "d_entries", entries, d_entries)) || (rc = ratio_pair(E, "perm", "d_perm", perm, d_perm))) return rc;
     FftRef d;
-    const GroupVTable *vt;
+    const FieldVTable *vt;
     if ((rc = ratio_domain(E, domain, m, &d, &vt))) return rc;
     const size_t mn = m << d->log2n, zbytes = vt->scalar_bytes << d->log2n;
     if (ratio_overlap(out, d_out, zbytes, entries, d_entries, m * zbytes) || ratio_overlap(out, d_out, zbytes, perm, d_perm, mn * 8))
@@ -1711,7 +1723,7 @@ GMSM_EXPORT int gmsm_iop_ratio_shuffled(uint64_t domain, const uint64_t *num, co
     if (!beta) return fail(GMSM_ERR_ARG, std::string(E) + ": beta must not be null");
     if ((rc = ratio_pair(E, "num", "d_num", num, d_num)) || (rc = ratio_pair(E, "den", "d_den", den, d_den))) return rc;
     FftRef d;
-    const GroupVTable *vt;
+    const FieldVTable *vt;
     if ((rc = ratio_domain(E, domain, m, &d, &vt))) return rc;
     const size_t zbytes = vt->scalar_bytes << d->log2n;
     if (ratio_overlap(out, d_out, zbytes, num, d_num, m * zbytes) || ratio_overlap(out, d_out, zbytes, den, d_den, m * zbytes)) return ratio_aliases(E);
@@ -1748,7 +1760,7 @@ GMSM_EXPORT int gmsm_iop_to_basis(uint64_t domain, uint64_t *a, void *d_a, size_
     if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
     if (len > ((size_t)1 << d->log2n))
         return fail(GMSM_ERR_ARG, std::string(E) + ": len " + std::to_string(len) + " is larger than the domain's cardinality");
-    const GroupVTable *vt = fr_vtable(d->group);
+    const FieldVTable *vt = fr_vtable(d->group);
     Context *ctx;
     if ((rc = enter_on(d->device, &ctx))) return rc;  // the domain decides the device
     if ((rc = check_device_vector(E, "d_a", d_a, ctx->device))) return rc;
@@ -1758,8 +1770,7 @@ GMSM_EXPORT int gmsm_iop_to_basis(uint64_t domain, uint64_t *a, void *d_a, size_
 GMSM_EXPORT int gmsm_iop_evaluate(int group, const uint64_t *polys, const void *d_polys, size_t k, size_t len, size_t size, int basis,
                                   const uint32_t *layouts, unsigned shift, const uint64_t *coset, const uint64_t *x, void *hip_stream,
                                   uint64_t *out_values) {
-    const GroupVTable *vt = fr_vtable(group);
-    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    FR_OR_FAIL(group);
     const char *E = "gmsm_iop_evaluate";
     if (k == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": no polynomial (k == 0)");
     if (len == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": empty polynomial (len == 0)");
@@ -1795,7 +1806,7 @@ GMSM_EXPORT int gmsm_iop_divide_by_x_minus_one(uint64_t domain_small, uint64_t d
     if (!small || !big) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
     if ((small->group & ~1) != (big->group & ~1)) return fail(GMSM_ERR_ARG, std::string(E) + ": the two domains are of different curves");
     if (small->log2n > big->log2n) return fail(GMSM_ERR_ARG, std::string(E) + ": the small domain is larger than the big one");
-    const GroupVTable *vt = fr_vtable(big->group);
+    const FieldVTable *vt = fr_vtable(big->group);
     const size_t bytes = vt->scalar_bytes << big->log2n;
     if (ratio_overlap(out, d_out, bytes, a, d_a, bytes)) return ratio_aliases(E);
     Context *ctx;
@@ -1858,8 +1869,7 @@ GMSM_EXPORT int gmsm_iop_evaluate_expression(int group, uint64_t domain, const u
                                              size_t n_consts, const uint64_t *const *polys, const void *const *d_polys, size_t m, size_t len,
                                              const size_t *sizes, const int64_t *shifts, const uint32_t *layouts, int out_layout, void *hip_stream,
                                              uint64_t *out, void *d_out) {
-    const GroupVTable *vt = fr_vtable(group);
-    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    FR_OR_FAIL(group);
     const char *E = "gmsm_iop_evaluate_expression";
     if (len == 0) return GMSM_OK;
     if (m == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": need at least one input (m == 0)");
@@ -1940,8 +1950,7 @@ static int multilin_len(const char *E, size_t len, size_t scalar_bytes, unsigned
 }
 
 GMSM_EXPORT int gmsm_multilin_fold(int group, uint64_t *a, void *d_a, size_t len, const uint64_t *r, void *hip_stream) {
-    const GroupVTable *vt = fr_vtable(group);
-    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    FR_OR_FAIL(group);
     const char *E = "gmsm_multilin_fold";
     unsigned n;
     int rc = multilin_len(E, len, vt->scalar_bytes, &n);
@@ -1956,8 +1965,7 @@ GMSM_EXPORT int gmsm_multilin_fold(int group, uint64_t *a, void *d_a, size_t len
 
 GMSM_EXPORT int gmsm_multilin_evaluate(int group, const uint64_t *m, const void *d_m, size_t len, const uint64_t *coords, size_t ncoords,
                                        void *hip_stream, uint64_t *out_value) {
-    const GroupVTable *vt = fr_vtable(group);
-    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    FR_OR_FAIL(group);
     const char *E = "gmsm_multilin_evaluate";
     unsigned n;
     int rc = multilin_len(E, len, vt->scalar_bytes, &n);
@@ -1974,8 +1982,7 @@ GMSM_EXPORT int gmsm_multilin_evaluate(int group, const uint64_t *m, const void 
 
 GMSM_EXPORT int gmsm_multilin_eq(int group, const uint64_t *q, size_t n, const uint64_t *scale, int accumulate, void *hip_stream, uint64_t *out,
                                  void *d_out) {
-    const GroupVTable *vt = fr_vtable(group);
-    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    FR_OR_FAIL(group);
     const char *E = "gmsm_multilin_eq";
     if (n >= 8 * sizeof(size_t) || ((size_t)1 << n) > ((size_t)1 << 62) / vt->scalar_bytes)
         return fail(GMSM_ERR_ARG, std::string(E) + ": n = " + std::to_string(n) + ": 2^n elements are beyond what size_t indexes");
@@ -1995,8 +2002,7 @@ GMSM_EXPORT int gmsm_multilin_eq(int group, const uint64_t *q, size_t n, const u
 GMSM_EXPORT int gmsm_gkr_claim_new(int group, const uint32_t *prog, size_t prog_len, const uint64_t *consts, size_t n_consts, size_t degree,
                                    const uint64_t *const *tables, const void *const *d_tables, size_t m, size_t len, const uint64_t *points, size_t k,
                                    const uint64_t *comb, void *hip_stream, uint64_t *out_gj, uint64_t *out_handle) {
-    const GroupVTable *vt = fr_vtable(group);
-    if (!vt) return fail(GMSM_ERR_ARG, "unknown group id");
+    FR_OR_FAIL(group);
     const char *E = "gmsm_gkr_claim_new";
     unsigned n;
     int rc = multilin_len(E, len, vt->scalar_bytes, &n);
@@ -2037,7 +2043,7 @@ GMSM_EXPORT int gmsm_gkr_claim_new(int group, const uint32_t *prog, size_t prog_
 }
 
 // The claim of a handle, locked for one call; refuses an unknown handle and a finished claim
-static int gkr_claim(const char *E, uint64_t handle, const void *r, const void *out, GkrRef *c, const GroupVTable **vt) {
+static int gkr_claim(const char *E, uint64_t handle, const void *r, const void *out, GkrRef *c, const FieldVTable **vt) {
     if (!(*c = g_gkr.get(handle))) return fail(GMSM_ERR_ARG, "unknown gkr claim handle");
     if (!r || !out) return fail(GMSM_ERR_ARG, std::string(E) + ": r and the output must not be null");
     *vt = fr_vtable((*c)->group);
@@ -2047,7 +2053,7 @@ static int gkr_claim(const char *E, uint64_t handle, const void *r, const void *
 GMSM_EXPORT int gmsm_gkr_claim_next(uint64_t handle, const uint64_t *r, uint64_t *out_gj) {
     const char *E = "gmsm_gkr_claim_next";
     GkrRef c;
-    const GroupVTable *vt;
+    const FieldVTable *vt;
     int rc = gkr_claim(E, handle, r, out_gj, &c, &vt);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -2063,7 +2069,7 @@ GMSM_EXPORT int gmsm_gkr_claim_next(uint64_t handle, const uint64_t *r, uint64_t
 GMSM_EXPORT int gmsm_gkr_claim_final(uint64_t handle, const uint64_t *r, uint64_t *out_evals) {
     const char *E = "gmsm_gkr_claim_final";
     GkrRef c;
-    const GroupVTable *vt;
+    const FieldVTable *vt;
     int rc = gkr_claim(E, handle, r, out_evals, &c, &vt);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mu);

@@ -290,9 +290,7 @@ struct FftField {
             int rc;
             if ((rc = d->twiddles_rev_lz.ensure(half * sizeof(Fr)))) return rc;
             if ((rc = d->twiddles_inv_rev_lz.ensure(half * sizeof(Fr)))) return rc;
-            Fr gen, gen_inv;
-            memcpy(&gen, d->generator.data(), sizeof(Fr));
-            memcpy(&gen_inv, d->generator_inv.data(), sizeof(Fr));
+            const Fr gen = fr_from_limbs<Fr>(d->generator.data()), gen_inv = fr_from_limbs<Fr>(d->generator_inv.data());
             const unsigned blocks = (unsigned)((half + 255) / 256);
             hipLaunchKernelGGL((k_fft_pow_table<FrP>), dim3(blocks), dim3(256), 0, stream, powers_of(gen), lazy_shift(), half,
                                (Fr *)d->twiddles_rev_lz.ptr, d->log2n - 1);
@@ -313,10 +311,8 @@ struct FftField {
         int rc;
         if ((rc = d->coset.ensure(n * sizeof(Fr)))) return rc;
         if ((rc = d->coset_inv_scaled.ensure(n * sizeof(Fr)))) return rc;
-        Fr shift, shift_inv, card_inv_lz;
-        memcpy(&shift, d->shift.data(), sizeof(Fr));
-        memcpy(&shift_inv, d->shift_inv.data(), sizeof(Fr));
-        memcpy(&card_inv_lz, d->cardinality_inv_lz.data(), sizeof(Fr));
+        const Fr shift = fr_from_limbs<Fr>(d->shift.data()), shift_inv = fr_from_limbs<Fr>(d->shift_inv.data());
+        const Fr card_inv_lz = fr_from_limbs<Fr>(d->cardinality_inv_lz.data());
         const unsigned blocks = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL((k_fft_pow_table<FrP>), dim3(blocks), dim3(256), 0, stream, powers_of(shift), lazy_shift(), n, (Fr *)d->coset.ptr);
         hipLaunchKernelGGL((k_fft_pow_table<FrP>), dim3(blocks), dim3(256), 0, stream, powers_of(shift_inv), card_inv_lz, n,
@@ -339,8 +335,7 @@ struct FftField {
         if (coset && (rc = ensure_coset_tables(stream, d))) return rc;
         if (dif && n > 1 && (rc = ensure_rev_tables(stream, d))) return rc;
         const bool fused = n > 1;  // the scalings ride on the first / last pass
-        Fr card_inv_lz;
-        memcpy(&card_inv_lz, d->cardinality_inv_lz.data(), sizeof(Fr));
+        const Fr card_inv_lz = fr_from_limbs<Fr>(d->cardinality_inv_lz.data());
         // the two scalings of the transform (fft.go:43-82, :144-195): DIT input and DIF output are bit-reversed, so the
         // tables are read in bit-reversed order there
         const Fr *pre = (coset && !inverse) ? (const Fr *)d->coset.ptr : nullptr;

@@ -43,7 +43,7 @@
 
 namespace gmsm {
 
-constexpr unsigned GKR_TPB = 256;  // lanes of a workgroup; the round kernel halves it while its LDS exceeds EXPR_LDS_BYTES
+constexpr unsigned GKR_TPB = EXPR_TPB;  // lanes of a workgroup; the round kernel halves it while its LDS exceeds EXPR_LDS_BYTES (expr_lanes_for)
 
 // a[i] <- a[i] + r (a[i + half] - a[i]), i < half; the upper half is not written
 template <class FrP>
@@ -197,15 +197,6 @@ template <class FrP>
 struct GkrField {
     using Fr = Fp<FrP>;
 
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    };
-    static Fr elem(const uint64_t *p) {
-        Fr v;
-        memcpy(&v, p, sizeof v);
-        return v;
-    }
     static int grid(const char *E, size_t n, unsigned tpb, unsigned *blocks) {
         const size_t b = (n + tpb - 1) / tpb;
         if (b > 0x7fffffffu) return fail(GMSM_ERR_ARG, std::string(E) + ": len is too large for one launch");
@@ -245,9 +236,9 @@ struct GkrField {
         GMSM_LEASE_OR_FAIL(lease, ctx);
         Workspace &ws = *lease.w;
         void *v;
-        Drain drain{ws.stream};
+        DrainOnExit drain{ws.stream};
         int rc = stage_input(ws, ws.h2d_scalars, a, d_a, len * sizeof(Fr), {After::STREAM, caller}, &v);
-        if (rc || (rc = fold_launch(E, ws.stream, (Fr *)v, len, elem(r)))) return rc;
+        if (rc || (rc = fold_launch(E, ws.stream, (Fr *)v, len, fr_from_limbs<Fr>(r)))) return rc;
         if (a) HIP_TRY(hipMemcpyAsync(a, v, len / 2 * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));  // the upper half stays as it was
         HIP_TRY(hipStreamSynchronize(ws.stream));
         return GMSM_OK;
@@ -262,10 +253,10 @@ struct GkrField {
         const size_t need = ncoords ? len : 1;  // no fold: only element 0 is read
         if ((rc = ws.poly.ensure(need * sizeof(Fr)))) return rc;
         Fr *v = (Fr *)ws.poly.ptr;
-        Drain drain{ws.stream};
+        DrainOnExit drain{ws.stream};
         HIP_TRY(hipMemcpyAsync(v, m ? (const void *)m : d_m, need * sizeof(Fr), m ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ws.stream));
         for (size_t j = 0; j < ncoords; ++j)  // back to back: the stream orders them
-            if ((rc = fold_launch(E, ws.stream, v, len >> j, elem(coords + j * (sizeof(Fr) / 8))))) return rc;
+            if ((rc = fold_launch(E, ws.stream, v, len >> j, fr_from_limbs<Fr>(coords + j * (sizeof(Fr) / 8))))) return rc;
         HIP_TRY(hipMemcpyAsync(out_value, v, sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
         HIP_TRY(hipStreamSynchronize(ws.stream));
         return GMSM_OK;
@@ -281,10 +272,10 @@ struct GkrField {
         if ((rc = ws.poly.ensure((n + eq_scratch(n)) * sizeof(Fr)))) return rc;
         if (out && (rc = ws.h2d_scalars.ensure(total * sizeof(Fr)))) return rc;
         Fr *dq = (Fr *)ws.poly.ptr, *res = out ? (Fr *)ws.h2d_scalars.ptr : (Fr *)d_out;
-        Drain drain{ws.stream};
+        DrainOnExit drain{ws.stream};
         if (n) HIP_TRY(hipMemcpyAsync(dq, q, n * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
         if (out && accumulate) HIP_TRY(hipMemcpyAsync(res, out, total * sizeof(Fr), hipMemcpyHostToDevice, ws.stream));
-        if ((rc = eq_launch(E, ws.stream, dq, n, elem(scale), accumulate != 0, dq + n, res))) return rc;
+        if ((rc = eq_launch(E, ws.stream, dq, n, fr_from_limbs<Fr>(scale), accumulate != 0, dq + n, res))) return rc;
         if (out) HIP_TRY(hipMemcpyAsync(out, res, total * sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
         HIP_TRY(hipStreamSynchronize(ws.stream));
         return GMSM_OK;
@@ -292,13 +283,6 @@ struct GkrField {
 
     // ---- one sumcheck claim (GkrClaim, gmsm_context.h): its tables and small buffers are its own, its rounds run on its stream
     static size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-    // lanes of the round kernel's workgroup for a program of nregs registers: its file and the row of wave sums within
-    // EXPR_LDS_BYTES (16 registers: 64 lanes for every field; the MiMC gate's three: 256)
-    static unsigned lanes_for(unsigned nregs) {
-        unsigned lanes = GKR_TPB;
-        while (lanes > 64 && (size_t)(nregs + 1) * sizeof(Fr) * lanes > EXPR_LDS_BYTES) lanes >>= 1;
-        return lanes;
-    }
 
     // the round polynomial of the claim's tables, after folding them by r when fold is set; out_gj: degree + 1 elements (host)
     static int round(const char *E, GkrClaim &c, bool fold, const Fr &r, uint64_t *out_gj) {
@@ -314,7 +298,7 @@ struct GkrField {
         args.prog_len = c.prog_len, args.m = (uint32_t)c.m, args.degree = (uint32_t)c.degree, args.fold = fold ? 1u : 0u, args.nregs = c.nregs, args.pad = 0;
         args.r = r;
         const unsigned npts = (unsigned)c.degree + 1;
-        Drain drain{c.stream};
+        DrainOnExit drain{c.stream};
         hipLaunchKernelGGL((k_gkr_round<FrP>), dim3(blocks), dim3(lanes), (size_t)(c.nregs + 1) * sizeof(Fr) * lanes, c.stream, args);
         HIP_TRY(hipGetLastError());
         if (fold) c.len /= 2;
@@ -339,7 +323,8 @@ struct GkrField {
         (void)ctx;
         unsigned n = 0;
         while (((size_t)1 << n) < c.stride) ++n;
-        c.lanes = lanes_for(c.nregs);
+        // the round kernel's workgroup: register file and row of wave sums within EXPR_LDS_BYTES (16 registers: 64 lanes; MiMC's three: 256)
+        c.lanes = expr_lanes_for<Fr>(c.nregs + 1);
         const size_t max_blocks = (c.stride / 2 + 63) / 64, npts = c.degree + 1;
         c.prog_at = n_consts * sizeof(Fr);
         c.partials_at = c.prog_at + align16(c.prog_len * sizeof(uint32_t));
@@ -349,7 +334,7 @@ struct GkrField {
         if ((rc = c.small.ensure(scratch_at + eq_scratch(n) * sizeof(Fr))) || (rc = c.tables.ensure((c.m + 1) * c.stride * sizeof(Fr)))) return rc;
         unsigned char *small = (unsigned char *)c.small.ptr;
         Fr *T = (Fr *)c.tables.ptr;
-        Drain drain{c.stream};
+        DrainOnExit drain{c.stream};
         if (n_consts) HIP_TRY(hipMemcpyAsync(small, consts, n_consts * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
         HIP_TRY(hipMemcpyAsync(small + c.prog_at, prog, c.prog_len * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
         if (n) HIP_TRY(hipMemcpyAsync(small + q_at, points, k * n * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
@@ -358,17 +343,17 @@ struct GkrField {
                                    tables ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c.stream));
         Fr scale = Fr::one();
         for (size_t j = 0; j < k; ++j) {
-            if (j) scale = fp_mul(scale, elem(comb));
+            if (j) scale = fp_mul(scale, fr_from_limbs<Fr>(comb));
             if ((rc = eq_launch(E, c.stream, (const Fr *)(small + q_at) + j * n, n, scale, j != 0, (Fr *)(small + scratch_at), T))) return rc;
         }
         return round(E, c, false, Fr::zero(), out_gj);
     }
-    static int gkr_next(GkrClaim *claim, const uint64_t *r, uint64_t *out_gj) { return round("gmsm_gkr_claim_next", *claim, true, elem(r), out_gj); }
+    static int gkr_next(GkrClaim *claim, const uint64_t *r, uint64_t *out_gj) { return round("gmsm_gkr_claim_next", *claim, true, fr_from_limbs<Fr>(r), out_gj); }
     static int gkr_final(GkrClaim *claim, const uint64_t *r, uint64_t *out_evals) {
         GkrClaim &c = *claim;
         Fr *res = (Fr *)((unsigned char *)c.small.ptr + c.result_at);
-        Drain drain{c.stream};
-        hipLaunchKernelGGL((k_gkr_final<FrP>), dim3(1), dim3(64), 0, c.stream, (const Fr *)c.tables.ptr, c.stride, (unsigned)c.m, elem(r), res);
+        DrainOnExit drain{c.stream};
+        hipLaunchKernelGGL((k_gkr_final<FrP>), dim3(1), dim3(64), 0, c.stream, (const Fr *)c.tables.ptr, c.stride, (unsigned)c.m, fr_from_limbs<Fr>(r), res);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(out_evals, res, c.m * sizeof(Fr), hipMemcpyDeviceToHost, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream));

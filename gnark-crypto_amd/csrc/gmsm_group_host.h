@@ -202,8 +202,7 @@ struct GroupHost {
     static void fold_powers(const uint64_t *coeff, size_t n, uint64_t *out_scalars) {
         using Fr = Fp<FrP>;
         Fr *scalars = reinterpret_cast<Fr *>(out_scalars);
-        Fr g, s = Fr::one();
-        memcpy(&g, coeff, sizeof g);
+        Fr g = fr_from_limbs<Fr>(coeff), s = Fr::one();
         for (size_t i = 0; i < n; ++i) {
             scalars[i] = s;
             s = fp_mul(s, g);

@@ -79,6 +79,15 @@ __device__ __forceinline__ void expr_reg_write(uint4 *regs, unsigned reg, unsign
     for (unsigned p = 0; p < PIECES; ++p) regs[(reg * PIECES + p) * lanes + lane] = src[p];
 }
 
+// lanes of a workgroup whose LDS holds `rows` elements per lane (a program's register file; the GKR round adds a row of wave
+// sums): 256, halved while that exceeds EXPR_LDS_BYTES (never below a wave: 16 registers of 48 bytes x 64 lanes = 48 KiB)
+template <class Fr>
+static inline unsigned expr_lanes_for(unsigned rows) {
+    unsigned lanes = EXPR_TPB;
+    while (lanes > 64 && (size_t)rows * sizeof(Fr) * lanes > EXPR_LDS_BYTES) lanes >>= 1;
+    return lanes;
+}
+
 // out[idx(i)] = the program at index i = blockIdx.x * blockDim.x + threadIdx.x. Dynamic LDS: registers used x sizeof(Fr) x
 // blockDim.x bytes. The host has validated the program: every opcode is known, every register read was written before,
 // every input and constant index is in range, POINT comes with a table (or len = 1).
@@ -123,14 +132,6 @@ template <class FrP>
 struct IopExprField {
     using Fr = Fp<FrP>;
 
-    // lanes of a workgroup for a program of nregs registers: 256, halved while the file exceeds EXPR_LDS_BYTES (never below
-    // a wave: 16 registers of 48 bytes x 64 lanes = 48 KiB)
-    static unsigned lanes_for(unsigned nregs) {
-        unsigned lanes = EXPR_TPB;
-        while (lanes > 64 && (size_t)nregs * sizeof(Fr) * lanes > EXPR_LDS_BYTES) lanes >>= 1;
-        return lanes;
-    }
-
     // Enqueues the one kernel. prog / consts / inputs: device; tw: the domain's twiddles_lz when the program has a POINT
     // and len > 1, else null.
     static int run(hipStream_t stream, const uint32_t *prog, size_t prog_len, unsigned nregs, const Fr *consts, const ExprInput *inputs,
@@ -140,7 +141,7 @@ struct IopExprField {
         args.prog_len = (uint32_t)prog_len, args.log2len = 0, args.out_rev = out_rev ? 1u : 0u, args.pad = 0;
         while (((size_t)1 << args.log2len) < len) ++args.log2len;  // read only where len is a power of two
         args.unshift = tw ? fp_inv(FftField<FrP>::lazy_shift()) : Fr::one();
-        const unsigned lanes = lanes_for(nregs);
+        const unsigned lanes = expr_lanes_for<Fr>(nregs);
         const size_t blocks = (len + lanes - 1) / lanes;
         if (blocks > 0x7fffffffu) return fail(GMSM_ERR_ARG, "gmsm_iop_evaluate_expression: len is too large for one launch");
         hipLaunchKernelGGL((k_iop_expr<FrP>), dim3((unsigned)blocks), dim3(lanes), (size_t)nregs * sizeof(Fr) * lanes, stream, args);

@@ -209,13 +209,8 @@ struct IopPolyField {
     // The point the polynomial is really evaluated at (Evaluate, polynomial.go:106-125): x / coset for LagrangeCoset (0^-1 = 0),
     // then times Generator(size)^shift, shift in 1..5
     static Fr effective_point(const uint64_t *x, int basis, const uint64_t *coset, unsigned shift, size_t size) {
-        Fr xx;
-        memcpy(&xx, x, sizeof xx);
-        if (basis == IOP_LAGRANGE_COSET) {
-            Fr c;
-            memcpy(&c, coset, sizeof c);
-            xx = fp_mul(xx, fp_inv(c));
-        }
+        Fr xx = fr_from_limbs<Fr>(x);
+        if (basis == IOP_LAGRANGE_COSET) xx = fp_mul(xx, fp_inv(fr_from_limbs<Fr>(coset)));
         if (shift) {
             unsigned ls = 0;
             while (((size_t)1 << ls) < size) ++ls;
@@ -302,9 +297,7 @@ struct IopPolyField {
         if (!e.ready) {
             const size_t rho = (size_t)1 << (big->log2n - log2n);
             if (int rc = e.table.ensure(rho * sizeof(Fr))) return rc;
-            Fr g, w;
-            memcpy(&g, big->shift.data(), sizeof g);
-            memcpy(&w, big->generator.data(), sizeof w);
+            const Fr g = fr_from_limbs<Fr>(big->shift.data()), w = fr_from_limbs<Fr>(big->generator.data());
             Fr *tbl = (Fr *)e.table.ptr;
             hipLaunchKernelGGL((k_iop_xn_minus_one<FrP>), dim3((unsigned)((rho + 255) / 256)), dim3(256), 0, stream, FF::powers_of(FF::pow2k(w, log2n)),
                                FF::pow2k(g, log2n), rho, tbl);

@@ -188,11 +188,7 @@ struct PolyField {
         return GMSM_OK;
     }
 
-    static FftPowers<FrP> powers_of(const uint64_t *point) {
-        Fr a;
-        memcpy(&a, point, sizeof a);
-        return FftField<FrP>::powers_of(a);
-    }
+    static FftPowers<FrP> powers_of(const uint64_t *point) { return FftField<FrP>::powers_of(fr_from_limbs<Fr>(point)); }
 
     // F = sum_i gamma^i f_i (maxlen elements, device) from k polynomials concatenated in polys (lens[i] elements each);
     // off_len: 2k uint64 of device scratch
@@ -203,10 +199,8 @@ struct PolyField {
         for (size_t i = 0; i < k; ++i) ol[2 * i] = off, ol[2 * i + 1] = lens[i], off += lens[i];
         HIP_TRY(hipMemcpyAsync(off_len, ol.data(), ol.size() * 8, hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));  // `ol` is pageable host memory that goes out of scope
-        Fr g;
-        memcpy(&g, gamma, sizeof g);
         hipLaunchKernelGGL((k_poly_fold<FrP>), dim3((unsigned)((maxlen + 255) / 256)), dim3(256), 0, stream, polys, (const uint64_t *)off_len, k,
-                           maxlen, g, folded);
+                           maxlen, fr_from_limbs<Fr>(gamma), folded);
         HIP_TRY(hipGetLastError());
         return GMSM_OK;
     }

@@ -301,8 +301,7 @@ struct RatioField {
 
     // bg[j] = beta g^j 2^-s, j < m (g = FrMultiplicativeGen, 2^s = the factor the domain's twiddles carry)
     static void coset_table(const FftDomain *d, const Fr &beta, size_t m, Fr *bg) {
-        Fr g;
-        memcpy(&g, d->shift.data(), sizeof g);
+        const Fr g = fr_from_limbs<Fr>(d->shift.data());
         Fr acc = fp_mul(beta, fp_inv(FftField<FrP>::lazy_shift()));
         for (size_t j = 0; j < m; ++j) {
             bg[j] = acc;

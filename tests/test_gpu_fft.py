@@ -285,3 +285,70 @@ def test_fft_class_edges_2_pow_18(gm, oracle_mod, curve):
                     want = F.transform(a, inverse=inverse, decimation=dec, coset=coset)
                     assert (got == want).all(), (inverse, dec, coset)
     d.release()
+
+
+# ---- the scalar field's entries under a G2 group id. The Python wrappers always pass the G1 id; the C ABI takes either, and
+# both must reach the one table of the curve's scalar field.
+@pytest.mark.parametrize("curve", CURVE_NAMES)
+@pytest.mark.parametrize("logn", [4, 11])
+def test_scalar_field_entries_take_the_g2_id(gm, oracle_mod, curve, logn):
+    """A domain made with the G2 id, then gmsm_fft (every direction, decimation and coset choice), gmsm_fft_bit_reverse,
+    gmsm_poly_eval, gmsm_poly_div_x_minus_a and gmsm_fr_batch_invert with the G2 id: limb for limb what the G1 id gives, and
+    the oracle's values for the transforms; gmsm_iop_to_basis on the G2-made domain equals the one on a G1-made domain.
+    n = 16, and 2^11 so that a transform takes more than one pass."""
+    import ctypes
+    L = gm._lib.load()
+    F = oracle_mod.FFT(curve)
+    c = F.curve
+    n, nl = 1 << logn, c.fr_limbs
+    a = random_field_limbs(rng_for(88, logn, nl), c.r, nl, n)
+    point = random_field_limbs(rng_for(89, logn, nl), c.r, nl, 1)[0]
+    ptr = lambda v: v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+    def ok(rc):
+        assert rc == 0, gm._lib.last_error()
+
+    def run(gid):
+        out = {}
+        h = ctypes.c_uint64(0)
+        ok(L.gmsm_fft_domain_new(gid, n, ctypes.byref(h)))
+        for inverse in (0, 1):
+            for dec in (gm.fft.DIT, gm.fft.DIF):
+                for coset in (0, 1):
+                    v = a.copy()
+                    ok(L.gmsm_fft(h.value, ptr(v), None, n, inverse, dec, coset, None))
+                    out["fft", inverse, dec, coset] = v
+        v = a.copy()
+        ok(L.gmsm_fft_bit_reverse(gid, ptr(v), None, n, None))
+        out["bit_reverse"] = v
+        lens = (ctypes.c_size_t * 2)(n - 3, 3)
+        vals = np.zeros((2, nl), dtype=np.uint64)
+        ok(L.gmsm_poly_eval(gid, ptr(a), None, lens, 2, ptr(point), None, ptr(vals)))
+        out["poly_eval"] = vals
+        q, value = np.zeros((n - 1, nl), dtype=np.uint64), np.zeros(nl, dtype=np.uint64)
+        ok(L.gmsm_poly_div_x_minus_a(gid, ptr(a), None, n, ptr(point), None, ptr(q), None, ptr(value)))
+        out["poly_div"], out["poly_div_value"] = q, value
+        inv = np.zeros_like(a)
+        ok(L.gmsm_fr_batch_invert(gid, ptr(a), None, n, None, ptr(inv), None))
+        out["batch_invert"] = inv
+        v, layout = a.copy(), ctypes.c_int(0)
+        ok(L.gmsm_iop_to_basis(h.value, ptr(v), None, n, gm.iop.Canonical, gm.iop.Regular, gm.iop.Lagrange, None, ctypes.byref(layout)))
+        out["iop_to_basis"], out["iop_layout"] = v, np.array([layout.value])
+        ok(L.gmsm_fft_domain_release(h.value))
+        return out
+
+    g1 = run(gm._lib.GROUP_IDS[(c.name, "g1")])
+    g2 = run(gm._lib.GROUP_IDS[(c.name, "g2")])
+    assert g1.keys() == g2.keys()
+    for key in g1:
+        assert (g2[key] == g1[key]).all(), key
+    for inverse in (0, 1):
+        for dec in (gm.fft.DIT, gm.fft.DIF):
+            for coset in (0, 1):
+                want = F.transform(a, inverse=bool(inverse), decimation=dec, coset=bool(coset))
+                assert (g2["fft", inverse, dec, coset] == want).all(), (inverse, dec, coset)
+    assert (g2["bit_reverse"] == F.bit_reverse(a)).all()
+    fr = oracle_mod.Field(f"{c.name}_fr", nl)
+    one = fr.to_mont(np.array([1] + [0] * (nl - 1), dtype=np.uint64))
+    for i in (0, 1, n // 2, n - 1):  # (a random element is zero with probability 2^-253 at the most)
+        assert (fr.mul(a[i], g2["batch_invert"][i]) == one).all(), i
