@@ -16,3 +16,5 @@ from . import polynomial  # noqa: F401  (fr/polynomial mirror: polynomial.MultiL
 from . import fiatshamir  # noqa: F401  (fiat-shamir mirror: fiatshamir.Transcript, NewTranscript, Bind, ComputeChallenge; host only)
 from . import sumcheck  # noqa: F401  (fr/sumcheck mirror: sumcheck.Prove over a claims object)
 from . import gkr  # noqa: F401  (fr/gkr mirror: gkr.Gate, gkr.Gates, gkr.Wire, gkr.Circuit, gkr.WireAssignment.Complete, gkr.Prove; gkr.Claim is the device handle of one wire's sumcheck claim)
+from . import mimc  # noqa: F401  (fr/mimc mirror: mimc.NewMiMC with Write / Sum / Reset / State / SetState, mimc.Sum, mimc.GetConstants; mimc.SumBatch hashes many messages on the device)
+from . import merkletree  # noqa: F401  (accumulator/merkletree mirror over MiMC: merkletree.DeviceTree with Root and Prove, merkletree.VerifyProof on the host)

@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "gmsm_iop_to_basis", "gmsm_iop_evaluate", "gmsm_iop_divide_by_x_minus_one", "gmsm_iop_evaluate_expression",
     "gmsm_multilin_fold", "gmsm_multilin_evaluate", "gmsm_multilin_eq",
     "gmsm_gkr_claim_new", "gmsm_gkr_claim_next", "gmsm_gkr_claim_final", "gmsm_gkr_claim_release",
+    "gmsm_mimc_constants", "gmsm_mimc_hash", "gmsm_mimc_sum_batch",
+    "gmsm_merkle_new", "gmsm_merkle_info", "gmsm_merkle_root", "gmsm_merkle_prove", "gmsm_merkle_release",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
     "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_debug_run_layout", "gmsm_debug_fold_planes", "gmsm_debug_plane_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
@@ -240,6 +242,22 @@ def load():
     L.gmsm_gkr_claim_final.argtypes = [ctypes.c_uint64, u64p, u64p]
     L.gmsm_gkr_claim_release.restype = ctypes.c_int
     L.gmsm_gkr_claim_release.argtypes = [ctypes.c_uint64]
+    L.gmsm_mimc_constants.restype = ctypes.c_int
+    L.gmsm_mimc_constants.argtypes = [ctypes.c_int, u64p, ctypes.POINTER(ctypes.c_uint)]
+    L.gmsm_mimc_hash.restype = ctypes.c_int
+    L.gmsm_mimc_hash.argtypes = [ctypes.c_int, u64p, u64p, sz, u64p]
+    L.gmsm_mimc_sum_batch.restype = ctypes.c_int
+    L.gmsm_mimc_sum_batch.argtypes = [ctypes.c_int, u64p, vp, sz, sz, sz, u64p, vp, u64p, vp]
+    L.gmsm_merkle_new.restype = ctypes.c_int
+    L.gmsm_merkle_new.argtypes = [ctypes.c_int, u64p, vp, sz, sz, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.gmsm_merkle_info.restype = ctypes.c_int
+    L.gmsm_merkle_info.argtypes = [ctypes.c_uint64, szp, szp, ctypes.POINTER(ctypes.c_uint)]
+    L.gmsm_merkle_root.restype = ctypes.c_int
+    L.gmsm_merkle_root.argtypes = [ctypes.c_uint64, u64p]
+    L.gmsm_merkle_prove.restype = ctypes.c_int
+    L.gmsm_merkle_prove.argtypes = [ctypes.c_uint64, u64p, sz, u64p, u64p, vp]
+    L.gmsm_merkle_release.restype = ctypes.c_int
+    L.gmsm_merkle_release.argtypes = [ctypes.c_uint64]
     L.gmsm_get_stage_launches.restype = ctypes.c_int
     L.gmsm_get_stage_launches.argtypes = [vp, ctypes.c_int]
     ip = ctypes.POINTER(ctypes.c_int)

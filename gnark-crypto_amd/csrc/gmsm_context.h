@@ -194,6 +194,33 @@ struct GkrClaim {
     }
 };
 
+// One Merkle tree over MiMC (accumulator/merkletree over fr/mimc; gmsm_mimc.h) resident on a device: every level of sums, and
+// the leaves' data when the caller asked for it (a proof set starts with it). Shared ownership like FftDomain. Built once by
+// gmsm_merkle_new and read-only afterwards, so proofs of one tree may run side by side.
+struct MerkleTree {
+    int group = -1;
+    int device = -1;
+    size_t n = 0, leaf_len = 0;  // leaves, elements per leaf
+    unsigned depth = 0;          // levels above the leaves' sums: ceil(log2 n), the longest proof's siblings
+    size_t total = 0;            // nodes of all levels: n + ceil(n / 2) + ... + 1
+    DeviceBuffer nodes;          // level 0 (the leaves' sums), then each level right behind the one it is made from; the root is last
+    DeviceBuffer leaves;         // n x leaf_len elements (keep_leaves), else empty
+    std::vector<uint64_t> root;  // the root's limbs, on the host since the build
+    MerkleTree() = default;
+    MerkleTree(const MerkleTree &) = delete;
+    MerkleTree &operator=(const MerkleTree &) = delete;
+    ~MerkleTree() {
+        if (!nodes.ptr && !leaves.ptr) return;
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        if (device >= 0) (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+        nodes.release();
+        leaves.release();
+        (void)hipSetDevice(prev);
+    }
+};
+
 // Everything one in-flight MultiExp needs on the device: scratch buffers, a pinned host buffer for the window totals, a
 // stream of its own (used when the caller gives none) and the stage events. A context owns three of them so that the
 // asynchronous entry points (gmsm_multiexp_bases_submit / _collect) can keep two MultiExp calls in flight: the sort and
@@ -875,6 +902,16 @@ struct FieldVTable {
                    const void *const *d_tables, const uint64_t *points, size_t k, const uint64_t *comb, uint64_t *out_gj);
     int (*gkr_next)(GkrClaim *claim, const uint64_t *r, uint64_t *out_gj);
     int (*gkr_final)(GkrClaim *claim, const uint64_t *r, uint64_t *out_evals);
+    // fr/mimc and accumulator/merkletree over it (gmsm_mimc.h). mimc_constants and mimc_hash are host arithmetic. The engine has
+    // validated every argument; a tree comes with its shape set (MerkleTree: group, device, n, leaf_len, depth, total).
+    unsigned mimc_rounds;
+    void (*mimc_constants)(uint64_t *out);
+    void (*mimc_hash)(const uint64_t *state, const uint64_t *elems, size_t len, uint64_t *out);
+    int (*mimc_sum_batch)(Context &ctx, const uint64_t *msgs, const void *d_msgs, size_t count, size_t len, size_t stride, const uint64_t *state,
+                          hipStream_t stream, uint64_t *out, void *d_out);
+    int (*merkle_new)(Context &ctx, MerkleTree *tree, const uint64_t *leaves, const void *d_leaves, bool keep_leaves, hipStream_t stream);
+    int (*merkle_prove)(Context &ctx, MerkleTree *tree, const uint64_t *indices, size_t k, uint64_t *out_leaves, uint64_t *out_siblings,
+                        uint32_t *out_counts);
 };
 
 }  // namespace gmsm

@@ -2087,6 +2087,121 @@ GMSM_EXPORT int gmsm_gkr_claim_release(uint64_t handle) {
     return GMSM_OK;
 }
 
+// ------------------------------------------------------------------ fr/mimc and the Merkle tree over it (gmsm_mimc.h)
+using MerkleRef = std::shared_ptr<MerkleTree>;
+static HandleTable<MerkleTree> g_merkle;
+
+GMSM_EXPORT int gmsm_mimc_constants(int group, uint64_t *out, unsigned *out_rounds) {
+    FR_OR_FAIL(group);
+    if (!out && !out_rounds) return fail(GMSM_ERR_ARG, "gmsm_mimc_constants: out and out_rounds are both null");
+    if (out) vt->mimc_constants(out);
+    if (out_rounds) *out_rounds = vt->mimc_rounds;
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_mimc_hash(int group, const uint64_t *state, const uint64_t *elems, size_t len, uint64_t *out) {
+    FR_OR_FAIL(group);
+    const char *E = "gmsm_mimc_hash";
+    if (!out) return fail(GMSM_ERR_ARG, std::string(E) + ": out is null");
+    if (len && !elems) return fail(GMSM_ERR_ARG, std::string(E) + ": elems is null");
+    vt->mimc_hash(state, elems, len, out);
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_mimc_sum_batch(int group, const uint64_t *msgs, const void *d_msgs, size_t count, size_t len, size_t stride, const uint64_t *state,
+                                    void *hip_stream, uint64_t *out, void *d_out) {
+    FR_OR_FAIL(group);
+    const char *E = "gmsm_mimc_sum_batch";
+    if (count == 0) return GMSM_OK;
+    if (stride < len) return fail(GMSM_ERR_ARG, std::string(E) + ": stride = " + std::to_string(stride) + " is less than len = " + std::to_string(len));
+    int rc;
+    if (len) {
+        if ((rc = ratio_pair(E, "msgs", "d_msgs", msgs, d_msgs))) return rc;
+    } else if (msgs && d_msgs) {  // nothing is read: none is fine, two is a mistake
+        return fail(GMSM_ERR_ARG, std::string(E) + ": give at most one of msgs (host) / d_msgs (device)");
+    }
+    if ((rc = ratio_pair(E, "out", "d_out", out, d_out))) return rc;
+    const size_t limit = ((size_t)1 << 62) / vt->scalar_bytes;
+    if (count > limit || (len && stride > limit / count)) return fail(GMSM_ERR_ARG, std::string(E) + ": count * stride does not fit");
+    const size_t in_bytes = len ? ((count - 1) * stride + len) * vt->scalar_bytes : 0, out_bytes = count * vt->scalar_bytes;
+    if (in_bytes && ratio_overlap(out, d_out, out_bytes, msgs, d_msgs, in_bytes)) return ratio_aliases(E);
+    if (out && !len) {  // count copies of the state: no device work
+        for (size_t i = 0; i < count; ++i) vt->mimc_hash(state, nullptr, 0, out + i * (vt->scalar_bytes / 8));
+        return GMSM_OK;
+    }
+    Context *ctx;
+    if ((rc = enter_owner(d_msgs ? d_msgs : d_out, &ctx))) return rc;
+    if ((rc = check_device_vector(E, "d_msgs", d_msgs, ctx->device)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
+    return vt->mimc_sum_batch(*ctx, msgs, len ? d_msgs : nullptr, count, len, stride, state, (hipStream_t)hip_stream, out, d_out);
+}
+
+GMSM_EXPORT int gmsm_merkle_new(int group, const uint64_t *leaves, const void *d_leaves, size_t n, size_t leaf_len, int keep_leaves, void *hip_stream,
+                                uint64_t *out_handle) {
+    FR_OR_FAIL(group);
+    const char *E = "gmsm_merkle_new";
+    if (n == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": no leaf (n == 0)");
+    if (leaf_len == 0) return fail(GMSM_ERR_ARG, std::string(E) + ": empty leaves (leaf_len == 0)");
+    if (!out_handle) return fail(GMSM_ERR_ARG, std::string(E) + ": out_handle is null");
+    int rc = ratio_pair(E, "leaves", "d_leaves", leaves, d_leaves);
+    if (rc) return rc;
+    const size_t limit = ((size_t)1 << 61) / vt->scalar_bytes;
+    if (n > limit || leaf_len > limit / n) return fail(GMSM_ERR_ARG, std::string(E) + ": n * leaf_len does not fit");
+    Context *ctx;
+    if ((rc = enter_owner(d_leaves, &ctx)) || (rc = check_device_vector(E, "d_leaves", d_leaves, ctx->device))) return rc;
+    MerkleRef t = std::make_shared<MerkleTree>();
+    t->group = group & ~1, t->device = ctx->device, t->n = n, t->leaf_len = leaf_len;
+    for (size_t size = n;; size = (size + 1) / 2) {
+        t->total += size;
+        if (size == 1) break;
+        ++t->depth;
+    }
+    if ((rc = vt->merkle_new(*ctx, t.get(), leaves, d_leaves, keep_leaves != 0, (hipStream_t)hip_stream))) return rc;
+    *out_handle = g_merkle.add(t);
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_merkle_info(uint64_t handle, size_t *out_n, size_t *out_leaf_len, unsigned *out_depth) {
+    MerkleRef t = g_merkle.get(handle);
+    if (!t) return fail(GMSM_ERR_ARG, "unknown merkle tree handle");
+    if (out_n) *out_n = t->n;
+    if (out_leaf_len) *out_leaf_len = t->leaf_len;
+    if (out_depth) *out_depth = t->depth;
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_merkle_root(uint64_t handle, uint64_t *out_root) {
+    MerkleRef t = g_merkle.get(handle);
+    if (!t) return fail(GMSM_ERR_ARG, "unknown merkle tree handle");
+    if (!out_root) return fail(GMSM_ERR_ARG, "gmsm_merkle_root: out_root is null");
+    memcpy(out_root, t->root.data(), t->root.size() * sizeof(uint64_t));
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_merkle_prove(uint64_t handle, const uint64_t *indices, size_t k, uint64_t *out_leaves, uint64_t *out_siblings,
+                                  uint32_t *out_counts) {
+    const char *E = "gmsm_merkle_prove";
+    MerkleRef t = g_merkle.get(handle);
+    if (!t) return fail(GMSM_ERR_ARG, "unknown merkle tree handle");
+    if (k == 0) return GMSM_OK;
+    if (!indices || !out_counts || (t->depth && !out_siblings))
+        return fail(GMSM_ERR_ARG, std::string(E) + ": indices, out_siblings and out_counts must not be null");
+    if (out_leaves && !t->leaves.ptr) return fail(GMSM_ERR_ARG, std::string(E) + ": out_leaves is given, but the tree was built without keep_leaves");
+    const FieldVTable *vt = fr_vtable(t->group);
+    if (k > ((size_t)1 << 61) / (vt->scalar_bytes * (t->depth + t->leaf_len))) return fail(GMSM_ERR_ARG, std::string(E) + ": k does not fit");
+    for (size_t j = 0; j < k; ++j)
+        if (indices[j] >= t->n)
+            return fail(GMSM_ERR_ARG, std::string(E) + ": indices[" + std::to_string(j) + "] = " + std::to_string(indices[j]) + " is outside [0, " +
+                                          std::to_string(t->n) + ")");
+    Context *ctx;
+    if (int rc = enter_on(t->device, &ctx)) return rc;
+    return vt->merkle_prove(*ctx, t.get(), indices, k, out_leaves, out_siblings, out_counts);
+}
+
+GMSM_EXPORT int gmsm_merkle_release(uint64_t handle) {
+    if (!g_merkle.take(handle)) return fail(GMSM_ERR_ARG, "unknown merkle tree handle");  // the levels go with the last reference
+    return GMSM_OK;
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {
@@ -2451,6 +2566,7 @@ GMSM_EXPORT int gmsm_shutdown(void) {
         const auto sharded = g_sharded.drain();
         const auto ffts = g_fft.drain();
         const auto claims = g_gkr.drain();
+        const auto trees = g_merkle.drain();
     }
     int prev = 0;
     (void)hipGetDevice(&prev);

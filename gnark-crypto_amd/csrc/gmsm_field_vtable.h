@@ -4,6 +4,7 @@
 #include "gmsm_fflonk.h"    // gmsm_shplonk.h, gmsm_poly.h, gmsm_fft.h
 #include "gmsm_iop_poly.h"  // gmsm_ratio.h
 #include "gmsm_gkr.h"       // gmsm_iop_expr.h
+#include "gmsm_mimc.h"
 
 namespace gmsm {
 
@@ -339,6 +340,13 @@ struct FieldVTableOf {
     static constexpr auto gkr_new = &GK::gkr_new;
     static constexpr auto gkr_next = &GK::gkr_next;
     static constexpr auto gkr_final = &GK::gkr_final;
+    // ---- fr/mimc and the Merkle tree over it (gmsm_mimc.h)
+    using MF = MimcField<FrP>;
+    static constexpr auto mimc_constants = &MF::constants;
+    static constexpr auto mimc_hash = &MF::hash;
+    static constexpr auto mimc_sum_batch = &MF::sum_batch;
+    static constexpr auto merkle_new = &MF::merkle_new;
+    static constexpr auto merkle_prove = &MF::merkle_prove;
     static const FieldVTable *get() {
         static const FieldVTable vt = [] {  // filled by name, in the order of the struct's members, as VTableOf::get() is
             FieldVTable v{};
@@ -350,6 +358,8 @@ struct FieldVTableOf {
             GMSM_VT(poly_eval), GMSM_VT(poly_div), GMSM_VT(open_check), GMSM_VT(fr_batch_invert), GMSM_VT(ratio_copy), GMSM_VT(ratio_shuffled);
             GMSM_VT(iop_to_basis), GMSM_VT(iop_evaluate), GMSM_VT(iop_quotient), GMSM_VT(iop_expr);
             GMSM_VT(multilin_fold), GMSM_VT(multilin_evaluate), GMSM_VT(multilin_eq), GMSM_VT(gkr_new), GMSM_VT(gkr_next), GMSM_VT(gkr_final);
+            v.mimc_rounds = FrP::MIMC_ROUNDS;
+            GMSM_VT(mimc_constants), GMSM_VT(mimc_hash), GMSM_VT(mimc_sum_batch), GMSM_VT(merkle_new), GMSM_VT(merkle_prove);
 #undef GMSM_VT
             return v;
         }();

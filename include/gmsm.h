@@ -606,6 +606,45 @@ int gmsm_gkr_claim_next(uint64_t handle, const uint64_t *r, uint64_t *out_gj);
 int gmsm_gkr_claim_final(uint64_t handle, const uint64_t *r, uint64_t *out_evals);
 int gmsm_gkr_claim_release(uint64_t handle);
 
+/* ---- fr/mimc (ecc/<curve>/fr/mimc/mimc.go) and accumulator/merkletree over it (tree.go, verify.go) on the device
+ *      (gmsm_mimc.h). Conventions are those of gmsm_fr_batch_invert: Montgomery fr.Element limbs; a G2 group id names its
+ *      curve's scalar field; exactly one of each host / device pointer pair; device pointers 16-byte aligned and produced on
+ *      hip_stream; the call returns when its result is complete; every error the host can decide is GMSM_ERR_ARG with a
+ *      text, before any device work, and nothing is written. Digests are the reference's bit for bit.
+ *   The hash (Miyaguchi-Preneel, mimc.go:130-163): h starts at the state (0 when none is given); for each element m:
+ *      t <- m, then `rounds` times t <- (t + h + c_i)^5, then h <- (t + h) + h + m. rounds is 110 for BN254, 111 for
+ *      BLS12-381, 163 for BW6-761; c_i: Keccak-256 chained from "seed", read big-endian mod r (initConstants).
+ *   gmsm_mimc_constants: GetConstants. out (rounds elements, Montgomery limbs) and out_rounds may each be NULL, not both.
+ *   gmsm_mimc_hash: the digest of len elements (host) continued from state (NULL: 0) to out (host), in host arithmetic: it
+ *      never touches the device. This is the hash under a Fiat-Shamir transcript: a few blocks per challenge.
+ *   gmsm_mimc_sum_batch: count digests: message i is the len elements at element offset i * stride, stride >= len; every
+ *      message starts from state (host, NULL: 0). len == 0 gives count copies of the state. count == 0 is GMSM_OK and touches
+ *      nothing. The output may not overlap the input.
+ *   A tree is a HANDLE that owns every level of its sums in HBM (and its leaves' data with keep_leaves != 0). Leaf i is the
+ *      leaf_len elements at i * leaf_len; its sum is their MiMC, a node is the MiMC of its two children (the reference's
+ *      prefixes are commented out, tree.go:92-105), the shape is RFC 6962's for any n >= 1: an odd last node of a level moves up
+ *      unchanged. gmsm_shutdown releases every tree; gmsm_trim leaves them alone (their memory is in use).
+ *   gmsm_merkle_info: n, leaf_len and depth = ceil(log2 n), the longest path's number of siblings. NULL pointers are skipped.
+ *   gmsm_merkle_root: the root's limbs to out_root (host).
+ *   gmsm_merkle_prove: k paths in one gather launch. indices (host): k leaf indices. out_siblings (host): k * depth elements;
+ *      path j's siblings bottom up from j * depth, out_counts[j] of them (a level where the node is the odd last one has no
+ *      sibling), zeros behind. out_leaves (host, k * leaf_len elements; NULL: not wanted): the leaves' data, the first
+ *      element of a reference proof set; allowed only if the leaves were kept. k == 0 is GMSM_OK.
+ *   Errors (GMSM_ERR_ARG, with a text): an unknown group; a null required pointer, both or none of a pair; stride < len;
+ *      sizes that do not fit; an output that overlaps the input; n == 0 or leaf_len == 0; out_leaves without kept leaves;
+ *      an index >= n ("indices[j] = v is outside [0, n)"); "unknown merkle tree handle". ---- */
+int gmsm_mimc_constants(int group, uint64_t *out, unsigned *out_rounds);
+int gmsm_mimc_hash(int group, const uint64_t *state, const uint64_t *elems, size_t len, uint64_t *out);
+int gmsm_mimc_sum_batch(int group, const uint64_t *msgs, const void *d_msgs, size_t count, size_t len, size_t stride,
+                        const uint64_t *state, void *hip_stream, uint64_t *out, void *d_out);
+int gmsm_merkle_new(int group, const uint64_t *leaves, const void *d_leaves, size_t n, size_t leaf_len, int keep_leaves,
+                    void *hip_stream, uint64_t *out_handle);
+int gmsm_merkle_info(uint64_t handle, size_t *out_n, size_t *out_leaf_len, unsigned *out_depth);
+int gmsm_merkle_root(uint64_t handle, uint64_t *out_root);
+int gmsm_merkle_prove(uint64_t handle, const uint64_t *indices, size_t k, uint64_t *out_leaves, uint64_t *out_siblings,
+                      uint32_t *out_counts);
+int gmsm_merkle_release(uint64_t handle);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals

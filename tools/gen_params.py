@@ -84,7 +84,84 @@ def glv_block(glv):
     return out
 
 
-def cxx_field(prefix, q, n64, fft=None, glv=None):
+# ---- MiMC round constants (ecc/<curve>/fr/mimc/mimc.go, initConstants): rnd <- Keccak-256("seed"), then `rounds` times
+# rnd <- Keccak-256(rnd), c_i = rnd read big-endian mod r. Legacy Keccak (padding byte 0x01), not hashlib.sha3_256.
+_KECCAK_RC = []
+_KECCAK_ROT = [[0] * 5 for _ in range(5)]
+
+
+def _keccak_tables():
+    lfsr = 1
+    for _ in range(24):
+        rc = 0
+        for j in range(7):
+            if lfsr & 1:
+                rc ^= 1 << ((1 << j) - 1)
+            lfsr = (lfsr << 1) ^ (0x171 if lfsr & 0x80 else 0)
+        _KECCAK_RC.append(rc)
+    x, y = 1, 0
+    for t in range(24):
+        _KECCAK_ROT[x][y] = (t + 1) * (t + 2) // 2 % 64
+        x, y = y, (2 * x + 3 * y) % 5
+
+
+_keccak_tables()
+
+
+def keccak_f1600(a):
+    """a[x][y]: 25 lanes of 64 bits, in place."""
+    m = (1 << 64) - 1
+    rol = lambda v, n: ((v << n) | (v >> (64 - n))) & m if n else v
+    for rc in _KECCAK_RC:
+        c = [a[x][0] ^ a[x][1] ^ a[x][2] ^ a[x][3] ^ a[x][4] for x in range(5)]
+        d = [c[(x - 1) % 5] ^ rol(c[(x + 1) % 5], 1) for x in range(5)]
+        a = [[a[x][y] ^ d[x] for y in range(5)] for x in range(5)]
+        b = [[0] * 5 for _ in range(5)]
+        for x in range(5):
+            for y in range(5):
+                b[y][(2 * x + 3 * y) % 5] = rol(a[x][y], _KECCAK_ROT[x][y])
+        a = [[b[x][y] ^ (~b[(x + 1) % 5][y] & m & b[(x + 2) % 5][y]) for y in range(5)] for x in range(5)]
+        a[0][0] ^= rc
+    return a
+
+
+def legacy_keccak256(data):
+    rate = 136
+    msg = bytearray(data) + b"\x01" + bytes(-(len(data) + 1) % rate)
+    msg[-1] |= 0x80
+    a = [[0] * 5 for _ in range(5)]
+    for off in range(0, len(msg), rate):
+        for i in range(rate // 8):
+            a[i % 5][i // 5] ^= int.from_bytes(msg[off + 8 * i:off + 8 * i + 8], "little")
+        a = keccak_f1600(a)
+    return b"".join(a[i % 5][i // 5].to_bytes(8, "little") for i in range(4))
+
+
+MIMC_ROUNDS = {"bn254": 110, "bls12_381": 111, "bw6_761": 163}  # mimcNbRounds of each curve's fr/mimc
+
+
+def mimc_constants(q, rounds):
+    rnd = legacy_keccak256(b"seed")
+    out = []
+    for _ in range(rounds):
+        rnd = legacy_keccak256(rnd)
+        out.append(int.from_bytes(rnd, "big") % q)
+    return out
+
+
+def mimc_block(q, n64, rounds):
+    R = 1 << (64 * n64)
+    words = [w for c in mimc_constants(q, rounds) for w in limbs32(c * R % q, n64)]
+    out = "    /* MiMC (fr/mimc): round constants, canonical Montgomery form, MIMC_ROUNDS x N words */\n"
+    out += f"    static constexpr unsigned MIMC_ROUNDS = {rounds};\n"
+    out += f"    static constexpr uint32_t MIMC_C[{len(words)}] = {{\n"
+    per = 2 * n64
+    for i in range(0, len(words), per):
+        out += "        " + ", ".join(f"0x{x:08x}u" for x in words[i:i + per]) + ",\n"
+    return out + "    };\n"
+
+
+def cxx_field(prefix, q, n64, fft=None, glv=None, mimc=0):
     """constexpr 32-bit-limb parameter struct for the HIP kernels (folded into instruction literals).
     fft = (root_of_unity, max_order, mult_gen): the scalar field's FFT constants (fr/generator.go, fr/fft/domain.go)."""
     R = 1 << (64 * n64)
@@ -110,6 +187,8 @@ def cxx_field(prefix, q, n64, fft=None, glv=None):
         out += arr("MULT_GEN", gen * R % q)
     if glv is not None:
         out += glv_block(glv)
+    if mimc:
+        out += mimc_block(q, n64, mimc)
     out += "};\n"
     return out
 
@@ -219,7 +298,7 @@ def render_cxx():
         s += cxx_field(f"{c.name}_fp", c.p, c.fp_limbs)
         glv = curves.GlvParams(c)
         glv.check()
-        s += cxx_field(f"{c.name}_fr", c.r, c.fr_limbs, (c.fr_root_of_unity, c.fr_max_order, c.fr_mult_gen), glv)
+        s += cxx_field(f"{c.name}_fr", c.r, c.fr_limbs, (c.fr_root_of_unity, c.fr_max_order, c.fr_mult_gen), glv, MIMC_ROUNDS[c.name])
         s += group_consts(c)
         s += "\n"
     s += "}  // namespace gmsm\n"

@@ -1,4 +1,5 @@
-"""GKR sumcheck rounds and a whole gkr.Prove on one GPU: python tools/gkr_prove.py [out.json] (default profiles/gkr_prove.json).
+"""GKR sumcheck rounds and a whole gkr.Prove on one GPU: python tools/gkr_prove.py [--hash sha256|mimc] [out.json] (default
+profiles/gkr_prove.json).
 One GPU session; run it under a time limit (timeout 300 python tools/gkr_prove.py).
 
 BN254, device-resident assignments. Each row is the host clock around the blocking calls (each ends in a stream synchronise),
@@ -8,8 +9,9 @@ median of `reps` after a warm-up:
                            inputs, declared degree 7, one evaluation point, at 2^17 and 2^20 instances
   eq                       gmsm_multilin_eq at n = 20
   prove                    gkr.Prove of the reference benchmark's shape, mimcCircuit(91) (gkr_test.go:314-324, 445-475) at 2^17
-                           instances, over a sha256 transcript (the reference's benchmark hashes with MiMC, which is not part of
-                           this library; the transcript is host work either way); and WireAssignment.Complete before it
+                           instances, over a sha256 transcript or, with --hash mimc, over mimc.NewMiMC as the reference's
+                           benchmark hashes (the transcript is host work either way: a few blocks per challenge through
+                           gmsm_mimc_hash); and WireAssignment.Complete before it
 Beside each round two floors from numbers that do not come from the code under test:
   floor_copy_ms      the bytes it must move at the rate of a device-to-device copy measured in the same run (read plus write):
                      claim_new reads and writes the m tables, writes E and reads all m + 1; next reads m + 1 tables and writes
@@ -59,7 +61,15 @@ def product_rate():
 
 
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "gkr_prove.json")
+    argv = sys.argv[1:]
+    hash_name = "sha256"
+    if "--hash" in argv:
+        at = argv.index("--hash")
+        hash_name = argv[at + 1]
+        del argv[at:at + 2]
+    if hash_name not in ("sha256", "mimc"):
+        sys.exit("--hash takes sha256 or mimc")
+    path = argv[0] if argv else os.path.join(ROOT, "profiles", "gkr_prove.json")
     reps = int(os.environ.get("GKR_PROVE_REPS", "7"))
     c = gm.CURVES[CURVE]
     rng = np.random.default_rng([0x6B, 1])
@@ -130,9 +140,9 @@ def main():
     t0 = time.perf_counter()
     a = K.WireAssignment(c, {circuit[0]: ins[0].data_ptr(), circuit[1]: ins[1].data_ptr()}, nb_instances=n, device=True).Complete(circuit)
     t1 = time.perf_counter()
-    proof = K.Prove(circuit, a, gm.fiatshamir.WithHash(hashlib.sha256))
+    proof = K.Prove(circuit, a, gm.fiatshamir.WithHash(hashlib.sha256 if hash_name == "sha256" else gm.mimc.Factory(CURVE)))
     t2 = time.perf_counter()
-    row = {"what": "prove", "circuit": "mimcCircuit(91)", "logn": 17, "transcript": "sha256", "complete_ms": (t1 - t0) * 1e3,
+    row = {"what": "prove", "circuit": "mimcCircuit(91)", "logn": 17, "transcript": hash_name, "complete_ms": (t1 - t0) * 1e3,
            "prove_ms": (t2 - t1) * 1e3, "runs": 1, "proof_elements": sum(sum(len(p) for p in w.PartialSumPolys) + len(w.FinalEvalProof) for w in proof)}
     out["rows"].append(row)
     print(json.dumps(row), flush=True)
