@@ -157,11 +157,16 @@ def test_decompose_matches_partition_scalars(gm, oracle_mod, curve, which):
     edge = scalars_from_ints(c_, [0, 1, 2, c_.r - 1, c_.r - 2, (1 << 16) - 1, 1 << 16, 1 << 15, (1 << 15) - 1, (1 << 64) - 1, 1 << 64,
                                   (1 << 128) + 12345, c_.r >> 1])
     sc[: len(edge)] = edge
-    for c in [2, 3, 4, 5, 8, 9, 10, 11, 12, 13, 14, 15, 16]:  # 8, 9, 10, 12..16: the unrolled kernels of the window table; the rest generic
-        nwin = o.nb_chunks(c)
+    import frontend_cases as fc
+    vals = fc.ints_from_mont(c_, sc)
+    for c in range(2, 21):  # 8, 9, 10, 12..18, 20: the unrolled kernels of the window table; the rest generic
+        nwin = o.nb_chunks(c) if c <= 16 else fc.num_windows(c_.fr_bits, c)
         out = np.zeros((nwin, n), dtype=np.uint32)
         assert L.gmsm_debug_decompose(g.gid, P(sc), n, c, P(out)) == 0, gm._lib.last_error()
-        exp = o.partition_scalars(sc, c).astype(np.uint32)
+        if c <= 16:  # the reference's own digits are 16 bits wide
+            exp = o.partition_scalars(sc, c).astype(np.uint32)
+        else:        # beyond: the same rule on Python ints (tests/frontend_cases.py, pinned to the reference for c <= 16)
+            exp = np.array([[fc.code(d) for d in fc.recode(c_, v, c)] for v in vals], dtype=np.uint32).T
         assert (out == exp).all(), (curve, c)
 
 
