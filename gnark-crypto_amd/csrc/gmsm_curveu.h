@@ -34,9 +34,15 @@ GMSM_HD FpU<P> fpu_one() {
 // cheap exact test "a == 0 mod q" for a normalised product-class value a < 3q
 template <class P>
 GMSM_HD bool fpu_prod_is_zero(const FpU<P> &a) {
+    // The first limb against its three possible values decides all but 3 * 2^-W of the calls. The full comparison is cheap
+    // enough that the compiler would otherwise run it unconditionally (3 compares and an AND per limb on every iteration of
+    // the accumulation loop) and drop the branch; the empty volatile statement keeps it behind the branch.
     const uint32_t l0 = a.l[0];
-    if (l0 == 0u || l0 == P::UQ1[0] || l0 == P::UQ2[0]) return fpu_is_zero_lt3q(a);
-    return false;
+    if (l0 != 0u && l0 != P::UQ1[0] && l0 != P::UQ2[0]) return false;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("");
+#endif
+    return fpu_is_zero_lt3q(a);
 }
 
 // acc = [2](px, py), affine input (doubleMixed / doubleNegMixed, g1.go:933-985); px < 2, py < 6.
@@ -111,6 +117,29 @@ GMSM_HD void madd_s(XYZZU<P> &acc, bool &inf, const FpU<P> &px, const FpU<P> &py
         acc.zz = fpu_one<P>();
         acc.zzz = fpu_one<P>();
         inf = false;
+        return;
+    }
+    if constexpr (INL && FpuDual<P>::value) {
+        // the independent products in pairs, two chains per scan (gmsm_fieldu.h, "two products at once"): px ZZ with
+        // py ZZZ, P^2 with R^2 (R^2 moves ahead of the P == 0 test, which reads it on its rare side anyway), P PP with
+        // X PP, ZZ PP with ZZZ PPP. Y3 needs X3 and stays a scan of its own. Same values as the one-at-a-time form below.
+        const FpuPair<P> u = fpu_mul2<P, true>(px, acc.zz, py, acc.zzz);
+        const FpU<P> Pv = fps_sub<P>(u.r0, acc.x);
+        const FpU<P> Rv = fps_sub<P>(u.r1, acc.y);
+        const FpuPair<P> s = fpu_sqr2<P, true>(Pv, Rv);               // PP, RR
+        if (fpu_prod_is_zero(s.r0)) {                                 // same x (g1.go:846-854)
+            if (fpu_prod_is_zero(s.r1)) double_mixed_u<P, INL>(acc, px, negate ? fpu_neg4<P>(py_in) : py_in);  // P + P
+            else inf = true;                                          // P + (-P)
+            return;
+        }
+        const FpuPair<P> t = fpu_mul2<P, true>(Pv, s.r0, acc.x, s.r0);  // PPP, Q
+        const FpU<P> X3 = fps_sub_sub2<P>(s.r1, t.r0, t.r1);
+        const FpU<P> Y3 = fpu_mul_add<P, true>(fps_sub<P>(t.r1, X3), Rv, fps_neg<P>(acc.y), t.r0);
+        const FpuPair<P> z = fpu_mul2<P, true>(acc.zz, s.r0, acc.zzz, t.r0);
+        acc.x = X3;
+        acc.y = Y3;
+        acc.zz = z.r0;
+        acc.zzz = z.r1;
         return;
     }
     const FpU<P> Pv = fps_sub<P>(fsmul<INL>(px, acc.zz), acc.x);

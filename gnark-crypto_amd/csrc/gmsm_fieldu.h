@@ -348,6 +348,144 @@ GMSM_HD FpU<P> fpu_sqr(const FpU<P> &a) {
     return r;
 }
 
+// ------------------------------------------------------------------ two products at once
+// The scans above say `acc >>= W; acc += a*b; ...`, but the compiler reassociates every column into a fresh chain of
+// multiply-adds that starts from zero, plus one 64-bit addition (v_lshl_add_u64 ..., 0, ...) that joins it to the shifted
+// carry: 2L - 1 additions per scan which the 64-bit addend of v_mad_u64_u32 / v_mad_i64_i32 would take for nothing.
+// Making the running sum opaque after every accumulation (fpu_chain) removes them: the statement order becomes the
+// instruction order, the carry rides in the column's first multiply-add. But then the whole product is ONE dependency
+// chain, and the compiler must put a wait state after each opaque statement whose result the next instruction reads.
+// Measured on BN254 G1 2^20 (profiles/product_chain.md): chained single scans make k_accumulate_seg 1 % slower, and the
+// kernels that run one scan at a time at low occupancy much slower (k_fixup_seg 44 -> 60 us, k_reduce_serial 65 -> 79 us):
+// those live on the freedom to interleave columns. So fpu_mul, fpu_mul_add, fpu_mul_add4 and fpu_sqr stay as they are, and
+// the chained form exists only where a second chain fills the gaps: fpu_mul2 / fpu_sqr2 walk the columns of two
+// INDEPENDENT products together, one multiply-add of each in turn. No addition, no wait state, and each chain's latency is
+// the other one's issue slot. Same columns, same values as two calls of fpu_mul / fpu_sqr; the price is the second set of
+// Montgomery digits (L more registers) while the pair runs. On the host fpu_chain is nothing at all.
+template <class A>
+GMSM_HD void fpu_chain(A &acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(acc));  // opaque to the reassociation pass
+#else
+    (void)acc;
+#endif
+}
+// Which base fields run their mixed addition (gmsm_curveu.h, madd_s) on the pair scans: measured ahead for the 9-limb field
+// at three waves per SIMD (k_accumulate_seg -2.4 %, 168 registers, no scratch); GMSM_PRODUCT_PAIRS_MAXL=0 builds the
+// one-at-a-time form for comparison.
+#ifndef GMSM_PRODUCT_PAIRS_MAXL
+#define GMSM_PRODUCT_PAIRS_MAXL 9
+#endif
+template <class P> struct FpuDual { static constexpr bool value = P::UL <= GMSM_PRODUCT_PAIRS_MAXL; };
+
+template <class P>
+struct FpuPair {
+    FpU<P> r0, r1;
+};
+
+// {a*b, c*d} * 2^-(L*W) mod q: operands and results as fpu_mul
+template <class P, bool SIGNED = false>
+GMSM_HD FpuPair<P> fpu_mul2(const FpU<P> &a, const FpU<P> &b, const FpU<P> &c, const FpU<P> &d) {
+    constexpr int L = P::UL, W = P::UW;
+    constexpr uint32_t MASK = FpU<P>::MASK;
+    uint32_t m0[L], m1[L];
+    FpuPair<P> r;
+    using LA = LimbAcc<SIGNED>;
+    using A = typename LA::type;
+    A acc0 = 0, acc1 = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * L - 1; ++k) {
+        const int lo = k < L ? 0 : k - L + 1, hi = k < L ? k : L - 1;
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) {
+            acc0 += LA::mul(a.l[i], b.l[k - i]);
+            fpu_chain(acc0);
+            acc1 += LA::mul(c.l[i], d.l[k - i]);
+            fpu_chain(acc1);
+        }
+#pragma unroll
+        for (int i = (k < L ? 0 : k - L + 1); i < (k < L ? k : L); ++i) {
+            acc0 += LA::mul(m0[i], P::UQ[k - i]);
+            fpu_chain(acc0);
+            acc1 += LA::mul(m1[i], P::UQ[k - i]);
+            fpu_chain(acc1);
+        }
+        if (k < L) {
+            m0[k] = ((uint32_t)acc0 * P::UQINV) & MASK;
+            m1[k] = ((uint32_t)acc1 * P::UQINV) & MASK;
+            acc0 += LA::mul(m0[k], P::UQ[0]);
+            fpu_chain(acc0);
+            acc1 += LA::mul(m1[k], P::UQ[0]);
+            fpu_chain(acc1);
+        } else {
+            r.r0.l[k - L] = (uint32_t)acc0 & MASK;
+            r.r1.l[k - L] = (uint32_t)acc1 & MASK;
+        }
+        acc0 >>= W;
+        acc1 >>= W;
+    }
+    r.r0.l[L - 1] = (uint32_t)acc0;
+    r.r1.l[L - 1] = (uint32_t)acc1;
+    return r;
+}
+
+// {a*a, c*c} * 2^-(L*W) mod q: operands and results as fpu_sqr
+template <class P, bool SIGNED = false>
+GMSM_HD FpuPair<P> fpu_sqr2(const FpU<P> &a, const FpU<P> &c) {
+    constexpr int L = P::UL, W = P::UW;
+    constexpr uint32_t MASK = FpU<P>::MASK;
+    uint32_t m0[L], m1[L], d0[L], d1[L];
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+        d0[i] = a.l[i] << 1;
+        d1[i] = c.l[i] << 1;
+    }
+    FpuPair<P> r;
+    using LA = LimbAcc<SIGNED>;
+    using A = typename LA::type;
+    A acc0 = 0, acc1 = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * L - 1; ++k) {
+        const int lo = k < L ? 0 : k - L + 1;
+#pragma unroll
+        for (int i = lo; 2 * i < k; ++i) {
+            acc0 += LA::mul(d0[i], a.l[k - i]);
+            fpu_chain(acc0);
+            acc1 += LA::mul(d1[i], c.l[k - i]);
+            fpu_chain(acc1);
+        }
+        if ((k & 1) == 0) {
+            acc0 += LA::mul(a.l[k / 2], a.l[k / 2]);
+            fpu_chain(acc0);
+            acc1 += LA::mul(c.l[k / 2], c.l[k / 2]);
+            fpu_chain(acc1);
+        }
+#pragma unroll
+        for (int i = (k < L ? 0 : k - L + 1); i < (k < L ? k : L); ++i) {
+            acc0 += LA::mul(m0[i], P::UQ[k - i]);
+            fpu_chain(acc0);
+            acc1 += LA::mul(m1[i], P::UQ[k - i]);
+            fpu_chain(acc1);
+        }
+        if (k < L) {
+            m0[k] = ((uint32_t)acc0 * P::UQINV) & MASK;
+            m1[k] = ((uint32_t)acc1 * P::UQINV) & MASK;
+            acc0 += LA::mul(m0[k], P::UQ[0]);
+            fpu_chain(acc0);
+            acc1 += LA::mul(m1[k], P::UQ[0]);
+            fpu_chain(acc1);
+        } else {
+            r.r0.l[k - L] = (uint32_t)acc0 & MASK;
+            r.r1.l[k - L] = (uint32_t)acc1 & MASK;
+        }
+        acc0 >>= W;
+        acc1 >>= W;
+    }
+    r.r0.l[L - 1] = (uint32_t)acc0;
+    r.r1.l[L - 1] = (uint32_t)acc1;
+    return r;
+}
+
 // Out-of-line copies for the kernels whose instruction footprint matters more than a call (chain fixup, bucket
 // reduction: a fully inlined XYZZ addition is ~25 KB of code and those kernels would otherwise hold several copies,
 // overflowing the 64 KB instruction cache -- measured: 15x slower). The accumulation loop keeps the inlined forms.
