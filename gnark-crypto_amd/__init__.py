@@ -18,3 +18,4 @@ from . import sumcheck  # noqa: F401  (fr/sumcheck mirror: sumcheck.Prove over a
 from . import gkr  # noqa: F401  (fr/gkr mirror: gkr.Gate, gkr.Gates, gkr.Wire, gkr.Circuit, gkr.WireAssignment.Complete, gkr.Prove; gkr.Claim is the device handle of one wire's sumcheck claim)
 from . import mimc  # noqa: F401  (fr/mimc mirror: mimc.NewMiMC with Write / Sum / Reset / State / SetState, mimc.Sum, mimc.GetConstants; mimc.SumBatch hashes many messages on the device)
 from . import merkletree  # noqa: F401  (accumulator/merkletree mirror over MiMC: merkletree.DeviceTree with Root and Prove, merkletree.VerifyProof on the host)
+from . import fri  # noqa: F401  (fr/fri mirror: fri.RADIX_2_FRI.New with BuildProofOfProximity / VerifyProofOfProximity / Open / VerifyOpening; fri.Oracle is the device handle of the committed layers and their trees)

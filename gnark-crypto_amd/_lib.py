@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "gmsm_gkr_claim_new", "gmsm_gkr_claim_next", "gmsm_gkr_claim_final", "gmsm_gkr_claim_release",
     "gmsm_mimc_constants", "gmsm_mimc_hash", "gmsm_mimc_sum_batch",
     "gmsm_merkle_new", "gmsm_merkle_info", "gmsm_merkle_root", "gmsm_merkle_prove", "gmsm_merkle_release",
+    "gmsm_fri_commit", "gmsm_fri_info", "gmsm_fri_root", "gmsm_fri_fold", "gmsm_fri_layer", "gmsm_fri_query", "gmsm_fri_release",
     "gmsm_fflonk_next_divisor", "gmsm_fflonk_fold", "gmsm_fflonk_fold_commit", "gmsm_fflonk_open_w", "gmsm_fflonk_open_wprime",
     "gmsm_bases_precompute", "gmsm_bases_table_bits", "gmsm_debug_table_runs", "gmsm_debug_small_runs", "gmsm_debug_reduce_shape", "gmsm_debug_run_layout", "gmsm_debug_fold_planes", "gmsm_debug_plane_runs", "gmsm_multiexp_sharded", "gmsm_bases_register_sharded", "gmsm_multiexp_bases_sharded", "gmsm_set_devices",
     "gmsm_get_devices", "gmsm_set_option", "gmsm_get_option", "gmsm_trim", "gmsm_shutdown",
@@ -258,6 +259,20 @@ def load():
     L.gmsm_merkle_prove.argtypes = [ctypes.c_uint64, u64p, sz, u64p, u64p, vp]
     L.gmsm_merkle_release.restype = ctypes.c_int
     L.gmsm_merkle_release.argtypes = [ctypes.c_uint64]
+    L.gmsm_fri_commit.restype = ctypes.c_int
+    L.gmsm_fri_commit.argtypes = [ctypes.c_uint64, u64p, vp, sz, vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.gmsm_fri_info.restype = ctypes.c_int
+    L.gmsm_fri_info.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint)]
+    L.gmsm_fri_root.restype = ctypes.c_int
+    L.gmsm_fri_root.argtypes = [ctypes.c_uint64, ctypes.c_uint, u64p]
+    L.gmsm_fri_fold.restype = ctypes.c_int
+    L.gmsm_fri_fold.argtypes = [ctypes.c_uint64, u64p, u64p]
+    L.gmsm_fri_layer.restype = ctypes.c_int
+    L.gmsm_fri_layer.argtypes = [ctypes.c_uint64, ctypes.c_uint, u64p, vp]
+    L.gmsm_fri_query.restype = ctypes.c_int
+    L.gmsm_fri_query.argtypes = [ctypes.c_uint64, u64p, sz, u64p, u64p, u64p, vp]
+    L.gmsm_fri_release.restype = ctypes.c_int
+    L.gmsm_fri_release.argtypes = [ctypes.c_uint64]
     L.gmsm_get_stage_launches.restype = ctypes.c_int
     L.gmsm_get_stage_launches.argtypes = [vp, ctypes.c_int]
     ip = ctypes.POINTER(ctypes.c_int)

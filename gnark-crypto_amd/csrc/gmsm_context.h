@@ -221,6 +221,35 @@ struct MerkleTree {
     }
 };
 
+// One FRI oracle (ecc/bn254/fr/fri/fri.go, gmsm_fri.h) between its folds: the sorted evaluations of every layer built so far and
+// one Merkle tree per layer, all in HBM. Layer k is trees[k]->leaves (N >> k elements, leaf_len 1): the tree hashes the layer where
+// it lies, so there is no second copy of the leaves. A fold appends one layer and its tree; the last one (16 -> 8 elements) builds
+// no tree and leaves the Evaluation. Shared ownership like FftDomain; the Fiat-Shamir step between two folds is the caller's.
+struct FriOracle {
+    int group = -1;
+    int device = -1;
+    unsigned log2n = 0;             // of N, the domain's cardinality
+    unsigned nb_steps = 0;          // log2 N - 3 (rho = 8)
+    unsigned folds_done = 0;        // 0 .. nb_steps
+    std::shared_ptr<FftDomain> domain;  // its inverse twiddles are read by every fold
+    std::vector<std::unique_ptr<MerkleTree>> trees;  // min(folds_done + 1, nb_steps) of them
+    DeviceBuffer last;              // the 8 elements the last fold leaves
+    std::vector<uint64_t> evaluation;  // element 0 of them, on the host since that fold
+    std::mutex mu;                  // one call at a time
+    FriOracle() = default;
+    FriOracle(const FriOracle &) = delete;
+    FriOracle &operator=(const FriOracle &) = delete;
+    ~FriOracle() {
+        if (!last.ptr) return;
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        if (device >= 0) (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+        last.release();
+        (void)hipSetDevice(prev);
+    }
+};
+
 // Everything one in-flight MultiExp needs on the device: scratch buffers, a pinned host buffer for the window totals, a
 // stream of its own (used when the caller gives none) and the stage events. A context owns three of them so that the
 // asynchronous entry points (gmsm_multiexp_bases_submit / _collect) can keep two MultiExp calls in flight: the sort and
@@ -912,6 +941,13 @@ struct FieldVTable {
     int (*merkle_new)(Context &ctx, MerkleTree *tree, const uint64_t *leaves, const void *d_leaves, bool keep_leaves, hipStream_t stream);
     int (*merkle_prove)(Context &ctx, MerkleTree *tree, const uint64_t *indices, size_t k, uint64_t *out_leaves, uint64_t *out_siblings,
                         uint32_t *out_counts);
+    // fr/fri's prover (gmsm_fri.h). The engine has validated every argument and holds the oracle's lock; an oracle comes with its
+    // shape set (FriOracle: group, device, log2n, nb_steps, domain).
+    int (*fri_commit)(Context &ctx, FriOracle *oracle, const uint64_t *p, const void *d_p, size_t len, hipStream_t stream);
+    int (*fri_fold)(Context &ctx, FriOracle *oracle, const uint64_t *xi, uint64_t *out);
+    int (*fri_layer)(Context &ctx, FriOracle *oracle, unsigned step, uint64_t *out, void *d_out);
+    int (*fri_query)(Context &ctx, FriOracle *oracle, const uint64_t *positions, size_t count, uint64_t *out_pairs, uint64_t *out_leaf_sums,
+                     uint64_t *out_siblings, uint32_t *out_counts);
 };
 
 }  // namespace gmsm

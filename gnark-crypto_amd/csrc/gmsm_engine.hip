@@ -2202,6 +2202,111 @@ GMSM_EXPORT int gmsm_merkle_release(uint64_t handle) {
     return GMSM_OK;
 }
 
+// ------------------------------------------------------------------ fr/fri's prover (gmsm_fri.h)
+using FriRef = std::shared_ptr<FriOracle>;
+static HandleTable<FriOracle> g_fri;
+
+GMSM_EXPORT int gmsm_fri_commit(uint64_t domain, const uint64_t *p, const void *d_p, size_t len, void *hip_stream, uint64_t *out_oracle) {
+    const char *E = "gmsm_fri_commit";
+    FftRef d = g_fft.get(domain);
+    if (!d) return fail(GMSM_ERR_ARG, "unknown fft domain handle");
+    const FieldVTable *vt = fr_vtable(d->group);
+    const size_t N = (size_t)1 << d->log2n;
+    if (d->log2n < 4)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": the domain's cardinality " + std::to_string(N) + " is below 16 (rho = 8 times a size of at least 2)");
+    if (len > N) return fail(GMSM_ERR_ARG, std::string(E) + ": len = " + std::to_string(len) + " is more than the domain's cardinality " + std::to_string(N));
+    if (!out_oracle) return fail(GMSM_ERR_ARG, std::string(E) + ": out_oracle is null");
+    int rc = ratio_pair(E, "p", "d_p", p, d_p);
+    if (rc) return rc;
+    Context *ctx;
+    if ((rc = enter_on(d->device, &ctx)) || (rc = check_device_vector(E, "d_p", d_p, ctx->device))) return rc;
+    FriRef o = std::make_shared<FriOracle>();
+    o->group = d->group & ~1, o->device = d->device, o->log2n = d->log2n, o->nb_steps = d->log2n - 3, o->domain = d;
+    if ((rc = vt->fri_commit(*ctx, o.get(), p, d_p, len, (hipStream_t)hip_stream))) return rc;
+    *out_oracle = g_fri.add(o);
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_fri_info(uint64_t oracle, uint64_t *out_cardinality, unsigned *out_nb_steps, unsigned *out_folds_done) {
+    FriRef o = g_fri.get(oracle);
+    if (!o) return fail(GMSM_ERR_ARG, "unknown fri oracle handle");
+    std::lock_guard<std::mutex> lk(o->mu);
+    if (out_cardinality) *out_cardinality = (uint64_t)1 << o->log2n;
+    if (out_nb_steps) *out_nb_steps = o->nb_steps;
+    if (out_folds_done) *out_folds_done = o->folds_done;
+    return GMSM_OK;
+}
+
+// refuses a step whose layer is not built; the caller holds the oracle's lock
+static int fri_step(const char *E, const FriOracle &o, size_t step) {
+    if (step < o.trees.size()) return GMSM_OK;
+    return fail(GMSM_ERR_ARG, std::string(E) + ": step " + std::to_string(step) + " is not built (" + std::to_string(o.trees.size()) + " of " +
+                                  std::to_string(o.nb_steps) + " layers are)");
+}
+
+GMSM_EXPORT int gmsm_fri_root(uint64_t oracle, unsigned step, uint64_t *out_root) {
+    const char *E = "gmsm_fri_root";
+    FriRef o = g_fri.get(oracle);
+    if (!o) return fail(GMSM_ERR_ARG, "unknown fri oracle handle");
+    if (!out_root) return fail(GMSM_ERR_ARG, std::string(E) + ": out_root is null");
+    std::lock_guard<std::mutex> lk(o->mu);
+    if (int rc = fri_step(E, *o, step)) return rc;
+    const std::vector<uint64_t> &root = o->trees[step]->root;
+    memcpy(out_root, root.data(), root.size() * sizeof(uint64_t));
+    return GMSM_OK;
+}
+
+GMSM_EXPORT int gmsm_fri_fold(uint64_t oracle, const uint64_t *xi, uint64_t *out) {
+    const char *E = "gmsm_fri_fold";
+    FriRef o = g_fri.get(oracle);
+    if (!o) return fail(GMSM_ERR_ARG, "unknown fri oracle handle");
+    if (!xi || !out) return fail(GMSM_ERR_ARG, std::string(E) + ": xi and out must not be null");
+    std::lock_guard<std::mutex> lk(o->mu);
+    if (o->folds_done >= o->nb_steps)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": all " + std::to_string(o->nb_steps) + " folds are done");
+    Context *ctx;
+    if (int rc = enter_on(o->device, &ctx)) return rc;
+    return fr_vtable(o->group)->fri_fold(*ctx, o.get(), xi, out);
+}
+
+GMSM_EXPORT int gmsm_fri_layer(uint64_t oracle, unsigned step, uint64_t *out, void *d_out) {
+    const char *E = "gmsm_fri_layer";
+    FriRef o = g_fri.get(oracle);
+    if (!o) return fail(GMSM_ERR_ARG, "unknown fri oracle handle");
+    int rc = ratio_pair(E, "out", "d_out", out, d_out);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(o->mu);
+    if ((rc = fri_step(E, *o, step))) return rc;
+    Context *ctx;
+    if ((rc = enter_on(o->device, &ctx)) || (rc = check_device_vector(E, "d_out", d_out, ctx->device))) return rc;
+    return fr_vtable(o->group)->fri_layer(*ctx, o.get(), step, out, d_out);
+}
+
+GMSM_EXPORT int gmsm_fri_query(uint64_t oracle, const uint64_t *positions, size_t count, uint64_t *out_pairs, uint64_t *out_leaf_sums,
+                               uint64_t *out_siblings, uint32_t *out_counts) {
+    const char *E = "gmsm_fri_query";
+    FriRef o = g_fri.get(oracle);
+    if (!o) return fail(GMSM_ERR_ARG, "unknown fri oracle handle");
+    if (count == 0) return GMSM_OK;
+    if (!positions || !out_pairs || !out_leaf_sums || !out_siblings || !out_counts)
+        return fail(GMSM_ERR_ARG, std::string(E) + ": positions and the four outputs must not be null");
+    std::lock_guard<std::mutex> lk(o->mu);
+    int rc = fri_step(E, *o, count - 1);
+    if (rc) return rc;
+    for (size_t i = 0; i < count; ++i)
+        if (positions[i] >= o->trees[i]->n)
+            return fail(GMSM_ERR_ARG, std::string(E) + ": positions[" + std::to_string(i) + "] = " + std::to_string(positions[i]) + " is outside [0, " +
+                                          std::to_string(o->trees[i]->n) + ")");
+    Context *ctx;
+    if ((rc = enter_on(o->device, &ctx))) return rc;
+    return fr_vtable(o->group)->fri_query(*ctx, o.get(), positions, count, out_pairs, out_leaf_sums, out_siblings, out_counts);
+}
+
+GMSM_EXPORT int gmsm_fri_release(uint64_t oracle) {
+    if (!g_fri.take(oracle)) return fail(GMSM_ERR_ARG, "unknown fri oracle handle");  // the layers go with the last reference
+    return GMSM_OK;
+}
+
 // ------------------------------------------------------------------ fixed-base batch
 GMSM_EXPORT int gmsm_batch_scalar_mul(int group, const uint64_t *base_affine, const uint64_t *scalars, size_t n,
                                       uint64_t *out_affine) {
@@ -2567,6 +2672,7 @@ GMSM_EXPORT int gmsm_shutdown(void) {
         const auto ffts = g_fft.drain();
         const auto claims = g_gkr.drain();
         const auto trees = g_merkle.drain();
+        const auto oracles = g_fri.drain();
     }
     int prev = 0;
     (void)hipGetDevice(&prev);

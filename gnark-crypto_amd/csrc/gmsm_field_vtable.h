@@ -4,7 +4,7 @@
 #include "gmsm_fflonk.h"    // gmsm_shplonk.h, gmsm_poly.h, gmsm_fft.h
 #include "gmsm_iop_poly.h"  // gmsm_ratio.h
 #include "gmsm_gkr.h"       // gmsm_iop_expr.h
-#include "gmsm_mimc.h"
+#include "gmsm_fri.h"    // gmsm_mimc.h
 
 namespace gmsm {
 
@@ -347,6 +347,12 @@ struct FieldVTableOf {
     static constexpr auto mimc_sum_batch = &MF::sum_batch;
     static constexpr auto merkle_new = &MF::merkle_new;
     static constexpr auto merkle_prove = &MF::merkle_prove;
+    // ---- fr/fri's prover over both (gmsm_fri.h)
+    using FR = FriField<FrP>;
+    static constexpr auto fri_commit = &FR::commit;
+    static constexpr auto fri_fold = &FR::fold;
+    static constexpr auto fri_layer = &FR::layer;
+    static constexpr auto fri_query = &FR::query;
     static const FieldVTable *get() {
         static const FieldVTable vt = [] {  // filled by name, in the order of the struct's members, as VTableOf::get() is
             FieldVTable v{};
@@ -360,6 +366,7 @@ struct FieldVTableOf {
             GMSM_VT(multilin_fold), GMSM_VT(multilin_evaluate), GMSM_VT(multilin_eq), GMSM_VT(gkr_new), GMSM_VT(gkr_next), GMSM_VT(gkr_final);
             v.mimc_rounds = FrP::MIMC_ROUNDS;
             GMSM_VT(mimc_constants), GMSM_VT(mimc_hash), GMSM_VT(mimc_sum_batch), GMSM_VT(merkle_new), GMSM_VT(merkle_prove);
+            GMSM_VT(fri_commit), GMSM_VT(fri_fold), GMSM_VT(fri_layer), GMSM_VT(fri_query);
 #undef GMSM_VT
             return v;
         }();

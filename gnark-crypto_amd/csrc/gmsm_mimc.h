@@ -208,19 +208,26 @@ struct MimcField {
         } else if ((rc = stage_input(ws, ws.h2d_scalars, leaves, d_leaves, leaf_bytes, {After::STREAM, caller}, &in))) {
             return rc;
         }
+        if ((rc = merkle_build(E, ws.stream, t, (const Fr *)in))) return rc;
+        HIP_TRY(hipStreamSynchronize(ws.stream));
+        return GMSM_OK;
+    }
+    // The levels of t (its shape set, t.nodes large enough) over the leaves at `in`, and the copy of the root to the host, queued
+    // on s: what gmsm_merkle_new runs over the caller's leaves and a FRI oracle (gmsm_fri.h) over each of its layers.
+    static int merkle_build(const char *E, hipStream_t s, MerkleTree &t, const Fr *in) {
+        int rc;
         Fr *level = (Fr *)t.nodes.ptr;
-        if ((rc = batch_launch(E, ws.stream, (const Fr *)in, t.n, t.leaf_len, t.leaf_len, Fr::zero(), level))) return rc;
+        if ((rc = batch_launch(E, s, in, t.n, t.leaf_len, t.leaf_len, Fr::zero(), level))) return rc;
         size_t size = t.n;
         for (; size > MERKLE_TOP; level += size, size = (size + 1) / 2) {
             unsigned blocks;
             if ((rc = grid(E, (size + 1) / 2, &blocks))) return rc;
-            hipLaunchKernelGGL((k_merkle_level<FrP>), dim3(blocks), dim3(MIMC_TPB), 0, ws.stream, (const Fr *)level, size, level + size);
+            hipLaunchKernelGGL((k_merkle_level<FrP>), dim3(blocks), dim3(MIMC_TPB), 0, s, (const Fr *)level, size, level + size);
         }
-        if (size > 1) hipLaunchKernelGGL((k_merkle_top<FrP>), dim3(1), dim3(MIMC_TPB), 0, ws.stream, level, size);
+        if (size > 1) hipLaunchKernelGGL((k_merkle_top<FrP>), dim3(1), dim3(MIMC_TPB), 0, s, level, size);
         HIP_TRY(hipGetLastError());
         t.root.resize(sizeof(Fr) / 8);
-        HIP_TRY(hipMemcpyAsync(t.root.data(), (const Fr *)t.nodes.ptr + (t.total - 1), sizeof(Fr), hipMemcpyDeviceToHost, ws.stream));
-        HIP_TRY(hipStreamSynchronize(ws.stream));
+        HIP_TRY(hipMemcpyAsync(t.root.data(), (const Fr *)t.nodes.ptr + (t.total - 1), sizeof(Fr), hipMemcpyDeviceToHost, s));
         return GMSM_OK;
     }
 

@@ -645,6 +645,38 @@ int gmsm_merkle_prove(uint64_t handle, const uint64_t *indices, size_t k, uint64
                       uint32_t *out_counts);
 int gmsm_merkle_release(uint64_t handle);
 
+/* ---- fr/fri's prover (ecc/<curve>/fr/fri/fri.go, RADIX_2_FRI with rho = 8) on the device (gmsm_fri.h). Conventions are those
+ *      of the MiMC entries above. A FRI ORACLE is a handle that owns, in HBM, the sorted evaluations of every layer built so far
+ *      (sorted[2i] = e[i], sorted[2i + 1] = e[i + s/2]: the reference's sort) and one MiMC Merkle tree per layer, leaf = one
+ *      element. With N the domain's cardinality there are nb_steps = log2 N - 3 layers of N, N/2, ..., 16 elements. The
+ *      Fiat-Shamir transcript stays with the caller: bind a root, derive x_i, fold. gmsm_shutdown releases every oracle;
+ *      gmsm_trim leaves them alone. An oracle keeps its domain alive; one call at a time runs on an oracle.
+ *   gmsm_fri_commit: domain is a gmsm_fft_domain_new handle with N >= 16. p (host) or d_p (device, produced on hip_stream): len <= N
+ *      coefficients, zero padded to N, never modified. Runs FFT(DIF), BitReverse and sort as one transform and one gather, and
+ *      builds the tree of layer 0.
+ *   gmsm_fri_info: N, nb_steps and the number of folds done. NULL pointers are skipped.
+ *   gmsm_fri_root: the root of layer `step`'s tree to out_root (host); step < the number of layers built.
+ *   gmsm_fri_fold: foldPolynomialLagrangeBasis with the challenge xi (host) and the sort of its result in one pass: appends
+ *      layer folds_done + 1 and its tree and writes the new root to out (host). The last fold (16 -> 8 elements) builds no tree:
+ *      out receives the round's Evaluation.
+ *   gmsm_fri_layer: the N >> step sorted evaluations of a layer to out (host) or d_out (device).
+ *   gmsm_fri_query: the openings of a round in one launch and one copy back. positions (host): positions[i] is the queried
+ *      leaf of layer i, i < count <= the number of layers built. All outputs are on the host. out_pairs: 2 * count elements,
+ *      the leaves at positions[i] & ~1 and next to it. out_leaf_sums: count elements, the MiMC of leaf positions[i] (the
+ *      neighbour's ProofSet[1]). out_siblings: count * log2 N elements, path i's siblings bottom up from i * log2 N,
+ *      out_counts[i] of them, zeros behind. count == 0 is GMSM_OK.
+ *   Errors (GMSM_ERR_ARG, with a text, nothing written): "unknown fft domain handle"; a cardinality below 16; len > N; both
+ *      or none of p / d_p or of out / d_out; a null required pointer; a fold past nb_steps; a root, layer or query of a step
+ *      that is not built; a position >= its layer's size; "unknown fri oracle handle". ---- */
+int gmsm_fri_commit(uint64_t domain, const uint64_t *p, const void *d_p, size_t len, void *hip_stream, uint64_t *out_oracle);
+int gmsm_fri_info(uint64_t oracle, uint64_t *out_cardinality, unsigned *out_nb_steps, unsigned *out_folds_done);
+int gmsm_fri_root(uint64_t oracle, unsigned step, uint64_t *out_root);
+int gmsm_fri_fold(uint64_t oracle, const uint64_t *xi, uint64_t *out);
+int gmsm_fri_layer(uint64_t oracle, unsigned step, uint64_t *out, void *d_out);
+int gmsm_fri_query(uint64_t oracle, const uint64_t *positions, size_t count, uint64_t *out_pairs, uint64_t *out_leaf_sums,
+                   uint64_t *out_siblings, uint32_t *out_counts);
+int gmsm_fri_release(uint64_t oracle);
+
 /* ---- window-sharded pieces (multi-GPU: windows win_first, win_first+win_stride, ... of the c-bit decomposition are
  *      handled by this device; the tiny per-window totals are exchanged by the caller, e.g. one RCCL all-gather).
  *      out_xyzz (host) receives nwin_local x {X,Y,ZZ,ZZZ} extended-Jacobian window totals
