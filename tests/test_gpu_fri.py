@@ -1,8 +1,9 @@
 """fr/fri's prover on the device against the big-int model (tests/fri_model.py) over the MiMC model: the whole ProofOfProximity and
 OpeningProof byte for byte, at the smallest shapes at which each part can go wrong:
   - size 2: N = 16, one step, a 4-lane fold, a 16-leaf tree; size 3: padding to the next power of two;
-  - size 64: N = 512 = MERKLE_TOP, tree 0 is k_merkle_top alone; size 128: N = 1024, the first k_merkle_level and the first fold
-    to span more than one workgroup; BN254 also at 256;
+  - size 64: N = 512 = MERKLE_TOP, tree 0 is k_merkle_top alone; size 128: N = 1024, the first k_merkle_level and the first sort
+    to span more than one workgroup - the fold still runs in one (N / 4 = 256 = FRI_TPB lanes); BN254 also at 256;
+  - size 256 (N = 2048, N / 4 = 512) on the two wider fields: the first fold over two workgroups there, checked as size 4096 is;
   - the reference test's size 4096 (BN254), where the pure-Python MiMC model is too slow: every layer against the model's field
     arithmetic, every root against a merkletree.DeviceTree over that layer, the proof through the host verifier, an opening
     against Horner;
@@ -120,6 +121,45 @@ def test_reference_size_4096(gm):
             s.VerifyOpening(m, opening, proof)
             assert opening.ClaimedValue == fm.horner(P, ints, pow(P.gen, m, c.r))
         same_opening(s.Open(p, m), s.Open(o, m))
+    finally:
+        o.Release()
+        s.Release()
+
+
+@pytest.mark.parametrize("curve", ["bls12_381", "bw6_761"])
+def test_fold_across_workgroups(gm, curve):
+    """size 256: N = 2048, so the first fold has N / 4 = 512 lanes, two workgroups of FRI_TPB = 256 (size 128 folds in one); only
+    BN254 folds across workgroups elsewhere. As test_reference_size_4096, without the Python MiMC model: every layer against the
+    model's field arithmetic, every root against a DeviceTree over that layer, the proof through the host verifier."""
+    c, size = gm.CURVES[curve], 256
+    P = fm.Params(c, size)
+    assert P.N == 2048 and P.N // 4 == 2 * 256
+    p = _poly(c, size)
+    ints = to_ints(c, p)
+    s = gm.fri.RADIX_2_FRI.New(curve, size, gm.mimc.Factory(curve))
+    o = s.Commit(p)
+    try:
+        xis, fs = s._transcript()
+        fs.Bind(xis[0], s._marshal(0))
+        cur, g_inv = fm.sort(fm.evaluations(P, ints)), P.gen_inv
+        for i in range(P.nb_steps):
+            layer = o.layer(i)
+            assert layer.shape == (P.N >> i, c.fr_limbs) and to_ints(c, layer) == cur, (curve, i)
+            tree = gm.merkletree.DeviceTree(c, leaves=layer.reshape(-1, 1, c.fr_limbs), keep_leaves=False)
+            try:
+                assert tree.Root() == o.Root(i), (curve, i)
+            finally:
+                tree.Release()
+            fs.Bind(xis[i], o.Root(i))
+            xi = int.from_bytes(fs.ComputeChallenge(xis[i]), "big") % c.r
+            out = o.fold(from_ints(c, [xi]))
+            cur = fm.sort(fm.fold(cur, g_inv, xi, P))
+            g_inv = g_inv * g_inv % c.r
+            assert o.folds_done() == i + 1
+        assert len(cur) == 8 and to_ints(c, out)[0] == cur[0]
+        proof = s.BuildProofOfProximity(p)
+        assert proof.Rounds[0].Evaluation == cur[0] and len(proof.Rounds[0].Interactions) == P.nb_steps == 8
+        s.VerifyProofOfProximity(proof)
     finally:
         o.Release()
         s.Release()

@@ -4,7 +4,8 @@ kernel can go wrong:
     pointers on a non-default torch stream; the parts that must not be written
   - one sumcheck claim, round by round (claim_new, every next, final) with random challenges: every run walks half from its
     first value down to 1, so it crosses the one-workgroup / several-workgroups boundary of the reduction wherever it lies;
-    n = 13 gives 16 workgroups of partial sums at the largest workgroup
+    n = 13 gives 16 workgroups of partial sums at the largest workgroup; BW6-761 at n = 16 over a ten-register gate (64 lanes) and
+    BN254 at n = 18 (256 lanes) give 512, more than k_gkr_finish has lanes
   - the reference's eight golden proofs through gkr.Prove over a constant hash, with host and with device assignments
   - a random circuit with a sha256 transcript against the model's proof, which the model's Verify accepts
   - handle lifecycle and four threads with a claim each"""
@@ -17,6 +18,7 @@ import numpy as np
 import pytest
 
 import gkr_model as M
+import point_batch_cases as pc
 from conftest import random_scalars, rng_for
 
 pytestmark = pytest.mark.gpu
@@ -170,6 +172,7 @@ GATES = {
     "add8": (add8, 8, 1, False),
     "wide8": (wide8, 8, 8, False),
     "deg3_as_5": (lambda x, y: x * y * y + x, 2, 5, False),
+    "pairs8": (pc.pairs8, 8, 2, False),
 }
 
 
@@ -227,6 +230,8 @@ def claim_cases():
         for name in GATES:
             if name == "wide8" and curve == "bls12_381":
                 continue  # the smallest and the largest element size
+            if name == "pairs8":
+                continue  # the gate of test_claim_with_more_workgroups_than_lanes: wide8 has its register pressure at these sizes
             for n in (1, 2, 6, 7, 8, 9, 10, 13):
                 yield curve, name, n
 
@@ -237,6 +242,26 @@ def test_claim_round_by_round(gm, curve, name, n):
     for k in (1, 2, 3):
         rng = rng_for(0x6B04, CURVES.index(curve), list(GATES).index(name), n, k)
         run_claim(gm, c, name, n, k, rng, device=(k + n) % 2 == 0)
+
+
+def test_pairs_gate_leaves_sixty_four_lanes(gm):
+    """10 registers and the row of wave sums of 48-byte elements: 11 x 48 x 128 bytes exceed the round kernel's LDS budget"""
+    code = gm.gkr.Gate(pc.pairs8, 2).code("bw6_761", 8)
+    assert max((int(w) >> 8) & 0xFF for w in code.words) >= 9
+
+
+MANY_WORKGROUPS = pc.MANY_WORKGROUPS  # (curve, gate, n, k, lanes of the round kernel): 512 workgroups in the first round
+
+
+@pytest.mark.parametrize("curve,name,n,k,lanes", MANY_WORKGROUPS, ids=[f"{c}-{g}-{n}-{k}" for c, g, n, k, _ in MANY_WORKGROUPS])
+def test_claim_with_more_workgroups_than_lanes(gm, curve, name, n, k, lanes):
+    """The first round's 512 rows of partial sums are twice the lanes of k_gkr_finish, whose strided loop takes a second step
+    (and in the next round, at 256 rows, exactly one); the claim then halves its way down through 128 .. 2 workgroups to the
+    single-workgroup rounds that need no second launch (tests/test_point_batch_cases.py derives the counts from the host code)."""
+    c = curve_of(gm, curve)
+    assert (1 << (n - 1)) // lanes == 512
+    rng = rng_for(0x6B09, CURVES.index(curve), list(GATES).index(name), n, k)
+    run_claim(gm, c, name, n, k, rng, device=(k + n) % 2 == 0)
 
 
 @pytest.mark.parametrize("curve", CURVES)
